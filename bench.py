@@ -12,8 +12,23 @@ per-replay device times (HIP events between replays: min / median / max of warm-
 window, the settle window medians) and the sysfs sclk / mclk / power sampled over the timed
 window, so a slow box shows itself in the record.
 
-Usage:  python bench.py [--gpus N --steps K --warmup W]   (N>1: one rank per GPU via
-        torch.distributed.run; rank 0 prints ONE JSON line).
+A plain run does only that: set-up, warm-up, the K timed replays, the result line.  ``--full``
+adds everything else the line can carry, each a measurement of its own after the timed window:
+the host's enqueue cost of a replay on an idle queue, the in-step kernel trace and the re-issued
+roofline launches (``roofline``, ``families_in_step``) and the CPU baseline (``cpu_baseline``,
+unless --no-cpu-baseline); a plain run reports those fields as null.
+
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (float32):
+``loss`` (the value the step returns), and a fixed seeded sample of at most 4 Mi elements each
+of ``grad`` (the flat gradient buffer the backward filled) and ``param`` (the flat fp32 master
+weights after the AdamW update).  So that two runs with the same arguments compute the same
+thing whatever the settle phase took, the training state (weights, AdamW moments and step count,
+BatchNorm statistics, mask counter, loss scale, LR iteration) is then put back, just before the
+timed window, to what it was right after the graph capture: the K timed steps are steps 4 .. K+3
+of the seeded training run for every W.
+
+Usage:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N>1: one
+        rank per GPU via torch.distributed.run; rank 0 prints ONE JSON line).
 """
 from __future__ import annotations
 
@@ -83,7 +98,13 @@ def parse():
                    help="fall back to eager launches when the HIP-graph capture fails (default: exit 3)")
     p.add_argument("--loss-scaling", action="store_true",
                    help="config 5's AMP step: dynamic loss scaling (GradScaler) inside the captured step")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the CPU baseline, the in-step "
+                        "kernel trace and roofline re-launches, the idle-queue host enqueue cost")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's loss and seeded samples of its gradients and updated "
+                        "weights as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--dry-run", action="store_true",
                    help="rehearse the rank launch on the CPU (gloo all-reduce), no GPU work")
     p.add_argument("--cpu-steps", type=int, default=3)
@@ -213,6 +234,37 @@ def replay_stats(ms):
     if not v:
         return None
     return {"n": len(v), "min": round(v[0], 4), "median": round(v[len(v) // 2], 4), "max": round(v[-1], 4)}
+
+
+DUMP_SAMPLE = 4 << 20          # elements of each flat buffer written by --dump-outputs (16 MiB as float32)
+
+
+def training_state(model, opt, scaler):
+    """Every device tensor a training step carries over to the next one: master weights and their
+    16-bit shadow, AdamW moments and step count, the step-mask counter, BatchNorm batch counter
+    and running statistics, the loss scale."""
+    ts = [model.store.flat, model.store.shadow, opt.exp_avg, opt.exp_avg_sq, opt.step_t,
+          (model.__dict__.get("_mask_state") or (None, None))[1], getattr(model, "_nbt", None),
+          getattr(model, "_bnbuf", None)]
+    if scaler is not None:
+        ts += [scaler.scale_t, scaler.tracker, scaler.found_inf]
+    return [t for t in ts if t is not None]
+
+
+def dump_outputs(path, loss, store):
+    """--dump-outputs: ``loss`` whole, ``grad`` and ``param`` at the same seeded element sample
+    (every element when the buffer has no more than DUMP_SAMPLE)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = store.flat.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(12345)).to(store.flat.device)
+    arrays = {"loss": loss.detach().reshape(1), "grad": store.grad, "param": store.flat}
+    for name, t in arrays.items():
+        if idx is not None and t.numel() == n:
+            t = t[idx]
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def free_port() -> int:
@@ -361,12 +413,23 @@ def main():
                 raise SystemExit(3)
             graph = None
 
+    last_loss = static_loss if graph is not None else None
+
     def run_one():
+        nonlocal last_loss
         set_lr()
         if graph is not None:
             graph.replay()
         else:
-            step()
+            last_loss = step()
+
+    # --dump-outputs: the training state at this point (3 steps run; 2 with --no-graph), put back
+    # before the timed window
+    state = saved = None
+    if args.dump_outputs:
+        torch.cuda.synchronize()
+        state, it_saved = training_state(model, opt, scaler), it
+        saved = [t.clone() for t in state]
 
     def replays(n):
         """n steps with a HIP event between consecutive ones (on the stream the graph replays
@@ -407,11 +470,16 @@ def main():
     # the host's own cost of one replay (enqueue of every node), with the device queue empty:
     # if it approaches the device time per step, the step turns host-bound
     host_enq = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         torch.cuda.synchronize()
         h0 = time.perf_counter()
         run_one()
         host_enq.append((time.perf_counter() - h0) * 1e3)
+    if saved is not None:
+        for t, kept in zip(state, saved):
+            t.copy_(kept)
+        it = it_saved
+        del saved
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -424,6 +492,8 @@ def main():
             dist.barrier()
         elapsed = time.perf_counter() - t0
     timed_ms = timed_ms()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_loss, model.store)
     print(f"[bench] host enqueue {t_enq / args.steps * 1e3:.3f} ms/step of {elapsed / args.steps * 1e3:.3f}",
           file=sys.stderr)
     trace_n = int(os.environ.get("CMX_BENCH_TRACE", "0"))
@@ -467,13 +537,15 @@ def main():
     # collectives need all ranks); no optimizer step follows, so the gradient all-reduce hooks
     # are detached first.  They run last: their in-place re-launches leave the activations and
     # BN statistics meaningless.
-    from rgbx_semantic_segmentation_amd.roofline import measure_dominant, measure_gemm_family, measure_in_step
+    # All of it is --full's: a plain run stops at the timed window.
     workload = f"CMX-{args.backbone.replace('mit_', '').upper()} train step {args.height}x{args.width} " \
                f"bs={args.batch} K={args.classes}"
     shape = dict(backbone=args.backbone, H=args.height, W=args.width, B=args.batch, K=args.classes)
     # (CMX_BENCH_NO_ROOFLINE=1: skipped, for the PMC / kernel-trace passes, whose per-launch
     # records must be the graph replays' only)
-    skip = os.environ.get("CMX_BENCH_NO_ROOFLINE") == "1"
+    skip = os.environ.get("CMX_BENCH_NO_ROOFLINE") == "1" or not args.full
+    if not skip:
+        from rgbx_semantic_segmentation_amd.roofline import measure_dominant, measure_gemm_family, measure_in_step
     roof = families = None
     if not skip and graph is not None:
         try:
@@ -494,7 +566,7 @@ def main():
         roof["second"] = second
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:

@@ -13,7 +13,7 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_gemm.py tests/test_gpu_kern
   --timeout-method thread -k "float16 or fp16" > gpurun_out/pytest_fp16_$TAG.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "FAILED|passed|failed" gpurun_out/pytest_fp16_$TAG.log | tail -15
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 300 python -u bench.py --backbone mit_b5 --height 1024 --width 1024 --batch 1 --classes 19 \
+timeout -k 10 300 python -u bench.py --backbone mit_b5 --height 1024 --width 1024 --batch 1 --classes 19 --full \
   --dtype float16 --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/bench_config5_fp16_$TAG.json 2> gpurun_out/bench_config5_fp16_$TAG.err
 rc=$?; echo "bench rc=$rc"; cut -c1-600 gpurun_out/bench_config5_fp16_$TAG.json; [ $rc -eq 0 ] || exit $rc
 # per-dispatch kernel trace of the B2 bf16 step (scripts/step_trace.py / step_census.py read it)

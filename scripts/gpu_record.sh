@@ -12,8 +12,10 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out gpurun_out/profiles
 TAG=${1:?tag}
 SKIP_SUITE=${2:-}
-timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
-rc=$?; echo "bench rc=$rc"; cut -c1-400 gpurun_out/bench_$TAG.json; [ $rc -eq 0 ] || exit $rc
+# the record's bench line carries the roofline and the CPU baseline: --full (into $CMX_RECORD_DIR, default record/)
+REC=${CMX_RECORD_DIR:-record}; mkdir -p "$REC"
+timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$REC/bench_$TAG.json" 2> "$REC/bench_$TAG.err"
+rc=$?; echo "bench rc=$rc"; cut -c1-400 "$REC/bench_$TAG.json"; [ $rc -eq 0 ] || exit $rc
 CMX_BENCH_NO_ROOFLINE=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run -- python3 bench.py --steps 20 --warmup 5 \
   --no-cpu-baseline > gpurun_out/prof_$TAG.log 2>&1 || exit $?
 db=$(ls gpurun_out/prof_$TAG/*.db gpurun_out/prof_$TAG/*/*.db 2>/dev/null | head -1)
@@ -35,10 +37,10 @@ if [ -z "$SKIP_SUITE" ]; then
   rc=$?; echo "pytest rc=$rc"; tail -2 gpurun_out/pytest_gpu_$TAG.log; grep -E "^FAILED" gpurun_out/pytest_gpu_$TAG.log | head
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
-timeout -k 10 300 python -u bench.py --backbone mit_b0 --height 240 --width 320 --batch 1 --classes 9 --steps 20 --warmup 5 \
+timeout -k 10 300 python -u bench.py --backbone mit_b0 --height 240 --width 320 --batch 1 --classes 9 --steps 20 --warmup 5 --full \
   --no-cpu-baseline > gpurun_out/profiles/${TAG}_bench_config1.json 2>&1 || exit $?
-timeout -k 10 300 python -u bench.py --backbone mit_b4 --height 480 --width 640 --batch 4 --classes 9 --steps 10 --warmup 3 \
+timeout -k 10 300 python -u bench.py --backbone mit_b4 --height 480 --width 640 --batch 4 --classes 9 --steps 10 --warmup 3 --full \
   --no-cpu-baseline > gpurun_out/profiles/${TAG}_bench_config4.json 2>&1 || exit $?
-timeout -k 10 300 python -u bench.py --backbone mit_b5 --height 1024 --width 1024 --batch 1 --classes 19 --dtype float16 \
+timeout -k 10 300 python -u bench.py --backbone mit_b5 --height 1024 --width 1024 --batch 1 --classes 19 --dtype float16 --full \
   --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/profiles/${TAG}_bench_config5_fp16.json 2>&1 || exit $?
 grep -h -o '"value": [0-9.]*' gpurun_out/profiles/${TAG}_bench_config*.json

@@ -56,6 +56,42 @@ def test_gpus_2_launches_two_ranks_end_to_end():
     assert lines == [{"dry_run": True, "n_gpus": 2, "ranks_seen": 2}]
 
 
+def test_plain_and_full_arguments(monkeypatch):
+    """A plain run measures the headline only; --full and --dump-outputs are opt-in."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+@pytest.mark.parametrize("n", [1000, bench.DUMP_SAMPLE + 4096])
+def test_dump_outputs_writes_float32_arrays(tmp_path, n):
+    """--dump-outputs: loss whole; grad and param whole up to DUMP_SAMPLE elements, above it the
+    same seeded sample of both, identical from call to call."""
+    import types
+    import numpy as np
+    import torch
+    flat = torch.arange(n, dtype=torch.float32)
+    store = types.SimpleNamespace(flat=flat, grad=-flat)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(2.5, dtype=torch.float64), store)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("loss", "grad", "param")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"].tolist() == [2.5]
+    m = min(n, bench.DUMP_SAMPLE)
+    assert got["param"].shape == got["grad"].shape == (m,)
+    assert np.array_equal(got["grad"], -got["param"])              # the same elements of both buffers
+    assert sum(v.nbytes for v in got.values()) <= 64 * 1000 * 1000
+    if n <= bench.DUMP_SAMPLE:
+        assert np.array_equal(got["param"], flat.numpy())
+    else:
+        assert 0 <= got["param"].min() and got["param"].max() < n and len(np.unique(got["param"])) > m // 2
+    for k, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy"))
+
+
 def test_graph_streams_env():
     """bench.py sets the HIP graph executor's stream count (2) before torch loads the runtime, for
     one GPU and for every rank of an N-GPU run; CMX_GRAPH_STREAMS picks another count (0 = the
