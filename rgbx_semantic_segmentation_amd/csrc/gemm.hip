@@ -42,13 +42,57 @@
 #include <stdlib.h>
 
 using namespace gemmk;
-CMX_GEMM_FAST_EXTERN(bf16)
-CMX_GEMM_FAST_EXTERN(f16)
-CMX_GEMM_GENERIC_SHAPES(CMX_GEMM_GENERIC_EXTERN, float)
-CMX_GEMM_GENERIC_SHAPES(CMX_GEMM_GENERIC_EXTERN, bf16)
-CMX_GEMM_GENERIC_SHAPES(CMX_GEMM_GENERIC_EXTERN, f16)
+namespace gp = gemmplan;
+extern CMX_GEMM_FAST_INST(bf16)
+extern CMX_GEMM_FAST_INST(f16)
+extern CMX_GEMM_GENERIC_INST(float)
+extern CMX_GEMM_GENERIC_INST(bf16)
+extern CMX_GEMM_GENERIC_INST(f16)
+static_assert(gp::FAST_BK == FBK && gp::GENERIC_BK == BK, "gemm_plan.h counts k-tiles of the kernels' depth");
 
 namespace {
+// the launch-policy knobs as they stand now: read at every planned launch (eager call or graph
+// capture), so a cmx_tune takes effect at the next one
+gp::GemmKnobs gemm_knobs() {
+  gp::GemmKnobs k;                               // (the defaults)
+  k.tiles = cmx_knob("GEMM_TILES", k.tiles);
+  k.smallk = cmx_knob("GEMM_SMALLK", k.smallk);
+  k.t128 = cmx_knob("GEMM_T128", k.t128);
+  k.splitkw = cmx_knob("GEMM_SPLITKW", k.splitkw);
+  k.kw = cmx_knob("GEMM_KW", k.kw);
+  k.mid = cmx_knob("GEMM_MID", k.mid);
+  k.stream = cmx_knob("GEMM_STREAM", k.stream);
+  k.stream_k = cmx_knob("GEMM_STREAM_K", k.stream_k);
+  k.stream_bpc = cmx_knob("GEMM_STREAM_BPC", k.stream_bpc);
+  k.grouped_kt = cmx_knob("GROUPED_KT", k.grouped_kt);
+  return k;
+}
+
+// the kernel(s) a plan names: the one place a GemmLaunch becomes launches
+int launch_gemm(const gp::GemmLaunch& L, const GemmArgs& a, int tA, int tB, int dtype, hipStream_t s) {
+  bool ok = true;
+  if (L.path == gp::PATH_STREAM) {
+    if (dtype == 2) launch_stream<f16>(L, a, tB, s);
+    else launch_stream<bf16>(L, a, tB, s);
+  } else if (L.path == gp::PATH_TILE) ok = dtype == 2 ? launch_tile<f16>(L, a, tA, tB, s) : launch_tile<bf16>(L, a, tA, tB, s);
+  else if (dtype == 1) ok = launch_generic<bf16>(L, a, tA, tB, s);
+  else if (dtype == 2) ok = launch_generic<f16>(L, a, tA, tB, s);
+  else ok = launch_generic<float>(L, a, tA, tB, s);
+  CMX_REQUIRE(ok, CMX_ERR_LAUNCH, "gemm: no kernel for path %d, tile %d x %d, NS %d, KW %d", L.path, L.bm, L.bn, L.ns,
+              L.kw);
+  if (L.nsplit > 1) {
+    if (dtype == 1) launch_reduce<bf16>(L, a, s);
+    else if (dtype == 2) launch_reduce<f16>(L, a, s);
+    else launch_reduce<float>(L, a, s);
+  }
+  return CMX_OK;
+}
+
+// the plan's share of the kernel arguments
+void set_plan(GemmArgs& a, const gp::GemmLaunch& L) {
+  a.kt_per_split = L.kt_per_split; a.nsplit = L.nsplit; a.tiles_m = L.tiles_m; a.tiles_n = L.tiles_n;
+}
+
 // ============================================================================ grouped reduce
 // out (+)= sum over nblk partial rows, for many reductions in one launch: the split-K slabs of
 // the grouped weight gradients, the per-block dgamma / dbeta partials of LayerNorm backward and
@@ -114,16 +158,7 @@ size_t cmx_gemm_workspace(int G, int M, int N, int splitk) {
 }
 
 int cmx_gemm_splitk(int G, int M, int N, int K, int ones_col, int dtype) {
-  if (G <= 0 || M <= 0 || N <= 0 || K <= 0) return 1;
-  if (dtype == 1 || dtype == 2) return auto_split(G, M, N, K, ones_col);
-  // generic path: BK = 32, aim for ~1024 blocks with >= 8 k-tiles per split
-  const int nb = ones_col ? N : N;
-  const long tiles = (long)cdiv(M, M <= 64 ? 64 : 128) * cdiv(nb, nb <= 64 ? 64 : 128) * G;
-  const int nk = (K + BK - 1) / BK;
-  long s = 1024 / (tiles > 0 ? tiles : 1);
-  if (s > nk / 8) s = nk / 8;
-  if (s > 64) s = 64;
-  return s < 1 ? 1 : (int)s;
+  return gp::default_split(G, M, N, K, ones_col, dtype, gemm_knobs());
 }
 
 }  // extern "C"
@@ -152,53 +187,79 @@ struct UpSpec {
   int h[3], w[3], n, oH, oW;
 };
 
-int gemm_impl(const void* A, const void* A2, const void* B, void* C, const float* bias, const void* R,
-              const float* rscale, float* dbias, float* workspace, int G, int M, int N, int K, int K1, int64_t lda,
-              int64_t lda2, int64_t ldb, int64_t ldc, int64_t sA, int64_t sA2, int64_t sB, int64_t sC, int64_t sbias,
-              int64_t sdb, int rows_per_sample, int transA, int transB, int act, int out_mode, int ones_col, int splitk,
-              int dtype, hipStream_t s, const UpSpec* up, int scR = 0, int scH = 0, int scW = 0, int scC = 0,
-              int scHo = 0, int scWo = 0, int gh = 1, int64_t sAh = 0, int64_t sBh = 0, int64_t sCh = 0,
-              GemmPlan* plan = nullptr, const void* mask = nullptr, const LnTail* tail = nullptr,
-              const LnBwd* lnb = nullptr) {
+// one GEMM as an entry point describes it; an entry point names the fields it uses, the rest
+// keep these defaults
+struct GemmProblem {
+  const void* A = nullptr; const void* A2 = nullptr; const void* B = nullptr; void* C = nullptr;
+  const float* bias = nullptr; const void* R = nullptr; const float* rscale = nullptr; const void* mask = nullptr;
+  float* dbias = nullptr; float* workspace = nullptr;
+  int G = 0, M = 0, N = 0, K = 0, K1 = 0;                          // (K1: used with A2 only)
+  int64_t lda = 0, lda2 = 0, ldb = 0, ldc = 0, sA = 0, sA2 = 0, sB = 0, sC = 0, sbias = 0, sdb = 0;
+  int rows_per_sample = 1, transA = 0, transB = 0, act = 0, out_mode = 0, ones_col = 0;
+  int splitk = 0, dtype = 0;
+  int scR = 0, scH = 0, scW = 0, scC = 0, scHo = 0, scWo = 0;      // patch-scatter epilogue (scR > 0)
+  int gh = 1;                                                      // two-level batch
+  int64_t sAh = 0, sBh = 0, sCh = 0;
+  const UpSpec* up = nullptr;
+  const LnTail* tail = nullptr;
+  const LnBwd* lnb = nullptr;
+  GemmPlan* plan = nullptr;                                        // plan only, nothing launched (cmx_gemm_plan)
+};
+
+int gemm_impl(const GemmProblem& p, hipStream_t s) {
+  const int G = p.G, M = p.M, N = p.N, K = p.K, dtype = p.dtype, out_mode = p.out_mode, ones_col = p.ones_col;
+  const int transA = p.transA, transB = p.transB, gh = p.gh;
+  const LnTail* tail = p.tail;
+  const LnBwd* lnb = p.lnb;
+  const UpSpec* up = p.up;
   CMX_REQUIRE(G > 0 && M > 0 && N > 0 && K > 0, CMX_ERR_SHAPE, "gemm: empty problem G=%d M=%d N=%d K=%d", G, M, N, K);
   CMX_REQUIRE(dtype >= 0 && dtype <= 2, CMX_ERR_DTYPE, "gemm: unsupported dtype %d", dtype);
-  CMX_REQUIRE(out_mode >= 0 && out_mode <= 2 && act >= 0 && act <= 3, CMX_ERR_ARG, "gemm: out_mode/act");
-  CMX_REQUIRE(!(R && out_mode == 2), CMX_ERR_ARG, "gemm: residual with accumulate");
-  if (!A2) K1 = K;
+  CMX_REQUIRE(out_mode >= 0 && out_mode <= 2 && p.act >= 0 && p.act <= 3, CMX_ERR_ARG, "gemm: out_mode/act");
+  CMX_REQUIRE(!(p.R && out_mode == 2), CMX_ERR_ARG, "gemm: residual with accumulate");
+  const int K1 = p.A2 ? p.K1 : K;
   CMX_REQUIRE(K1 > 0 && K1 <= K && (K1 == K || !transA), CMX_ERR_SHAPE,
               "gemm: a second A segment needs transA = 0 (K1=%d K=%d)", K1, K);
-  CMX_REQUIRE(!R || rows_per_sample > 0, CMX_ERR_ARG, "gemm: rows_per_sample");
-  CMX_REQUIRE(!ones_col || (transB && dbias && N >= 2 && out_mode != 0 && !bias && !R && act == 0), CMX_ERR_ARG,
+  CMX_REQUIRE(!p.R || p.rows_per_sample > 0, CMX_ERR_ARG, "gemm: rows_per_sample");
+  CMX_REQUIRE(!ones_col || (transB && p.dbias && N >= 2 && out_mode != 0 && !p.bias && !p.R && p.act == 0), CMX_ERR_ARG,
               "gemm: ones_col (bias gradient) needs transB, dbias, fp32 output and no epilogue");
   CMX_REQUIRE((long)M * N < (1L << 31) && (long)M * K < (1L << 40), CMX_ERR_SHAPE, "gemm: problem too large");
-  const bool fast = dtype != 0 && fast_ok(A, A2, B, M, N, K, K1, lda, lda2, ldb, sA, sA2, sB, transA, transB, ones_col) &&
-                    sAh % 8 == 0 && sBh % 8 == 0;
+  const bool fast = dtype != 0 && fast_ok(p.A, p.A2, p.B, M, N, K, K1, p.lda, p.lda2, p.ldb, p.sA, p.sA2, p.sB, transA,
+                                          transB, ones_col) && p.sAh % 8 == 0 && p.sBh % 8 == 0;
   const int V = dtype == 0 ? 4 : 8;
   const int nb = ones_col ? N - 1 : N;
   const bool vec = (transA ? M : K) % V == 0 && (transB ? nb : K) % V == 0 && (K - K1) % V == 0 && (K1 == K || K1 % V == 0) &&
-                   lda % V == 0 && ldb % V == 0 && sA % V == 0 && sB % V == 0 && (!A2 || (lda2 % V == 0 && sA2 % V == 0)) &&
-                   ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && (!A2 || (uintptr_t)A2 % 16 == 0);
+                   p.lda % V == 0 && p.ldb % V == 0 && p.sA % V == 0 && p.sB % V == 0 &&
+                   (!p.A2 || (p.lda2 % V == 0 && p.sA2 % V == 0)) && ((uintptr_t)p.A % 16 == 0) &&
+                   ((uintptr_t)p.B % 16 == 0) && (!p.A2 || (uintptr_t)p.A2 % 16 == 0);
   CMX_REQUIRE(fast || K1 == K || K1 % BK == 0, CMX_ERR_SHAPE, "gemm: second A segment needs K1 %% %d == 0", BK);
-  if (splitk <= 0) splitk = fast ? auto_split(G, M, N, K, ones_col) : cmx_gemm_splitk(G, M, N, K, ones_col, 0);
-  CMX_REQUIRE(splitk == 1 || workspace, CMX_ERR_ARG, "gemm: split-K needs a workspace");
+  const int nup = up && up->n > 0 ? up->n : 0;
+  gp::GemmShape shape;
+  shape.G = G; shape.M = M; shape.N = N; shape.K = K; shape.transA = transA; shape.transB = transB;
+  shape.ones_col = ones_col; shape.dtype = dtype; shape.fast = fast; shape.splitk = p.splitk; shape.a2 = p.A2 != nullptr;
+  shape.row_ln = tail != nullptr; shape.ln_bwd = lnb != nullptr; shape.scC = p.scR > 0 ? p.scC : 0; shape.nup = nup;
+  shape.gh = gh; shape.tile_only = p.plan != nullptr;
+  const gp::GemmLaunch L = plan_gemm(shape, gemm_knobs(), cu_count());
+  const int splitk = L.nsplit;
+  CMX_REQUIRE((p.splitk > 0 ? p.splitk : splitk) == 1 || p.workspace, CMX_ERR_ARG, "gemm: split-K needs a workspace");
   GemmArgs a{};
-  a.A = A; a.A2 = A2; a.B = B; a.C = C; a.bias = bias; a.R = R; a.rscale = rscale; a.dbias = dbias; a.ws = workspace;
-  a.G = G; a.M = M; a.N = N; a.K = K; a.K1 = K1; a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1;
-  a.act = act; a.out_mode = out_mode; a.ones_col = ones_col; a.vec = vec;
-  CMX_REQUIRE(!mask || (out_mode == 0 && !ones_col && (uintptr_t)mask % 16 == 0 && (!R || R != mask)), CMX_ERR_ARG,
-              "gemm: a ReLU mask needs a plain store in C's layout");
-  a.mask = mask;
+  a.A = p.A; a.A2 = p.A2; a.B = p.B; a.C = p.C; a.bias = p.bias; a.R = p.R; a.rscale = p.rscale; a.dbias = p.dbias;
+  a.ws = p.workspace;
+  a.G = G; a.M = M; a.N = N; a.K = K; a.K1 = K1; a.rows_per_sample = p.rows_per_sample > 0 ? p.rows_per_sample : 1;
+  a.act = p.act; a.out_mode = out_mode; a.ones_col = ones_col; a.vec = vec;
+  CMX_REQUIRE(!p.mask || (out_mode == 0 && !ones_col && (uintptr_t)p.mask % 16 == 0 && (!p.R || p.R != p.mask)),
+              CMX_ERR_ARG, "gemm: a ReLU mask needs a plain store in C's layout");
+  a.mask = p.mask;
   // 8-column epilogue groups as aligned vectors: C (and R) rows start on 16-B boundaries
   const long esz = out_mode == 0 ? (dtype != 0 ? 2 : 4) : 4;
-  a.cvec = ((uintptr_t)C % 16 == 0) && (ldc * esz) % 16 == 0 && (sC * esz) % 16 == 0 &&
-           (!R || (uintptr_t)R % 16 == 0);
-  a.lda = lda; a.lda2 = lda2; a.ldb = ldb; a.ldc = ldc; a.sA = sA; a.sA2 = sA2; a.sB = sB; a.sC = sC;
-  a.sbias = sbias; a.sdb = sdb;
-  CMX_REQUIRE(gh >= 1 && (gh == 1 || (G % gh == 0 && !A2 && !bias && !R && !ones_col && !(up && up->n) && !scR)),
+  a.cvec = ((uintptr_t)p.C % 16 == 0) && (p.ldc * esz) % 16 == 0 && (p.sC * esz) % 16 == 0 &&
+           (!p.R || (uintptr_t)p.R % 16 == 0);
+  a.lda = p.lda; a.lda2 = p.lda2; a.ldb = p.ldb; a.ldc = p.ldc; a.sA = p.sA; a.sA2 = p.sA2; a.sB = p.sB; a.sC = p.sC;
+  a.sbias = p.sbias; a.sdb = p.sdb;
+  CMX_REQUIRE(gh >= 1 && (gh == 1 || (G % gh == 0 && !p.A2 && !p.bias && !p.R && !ones_col && !nup && !p.scR)),
               CMX_ERR_ARG, "gemm: a two-level batch (gh=%d) takes G %% gh == 0 and no A2 / bias / residual / "
               "bias-gradient / upsample / scatter", gh);
-  a.gh = gh; a.sAh = sAh; a.sBh = sBh; a.sCh = sCh;
-  if (up && up->n > 0) {
+  a.gh = gh; a.sAh = p.sAh; a.sBh = p.sBh; a.sCh = p.sCh;
+  if (nup) {
     CMX_REQUIRE(up->n <= 3 && G == 1 && !ones_col && N % 8 == 0 && (long)up->oH * up->oW > 0 &&
                 M % (up->oH * up->oW) == 0, CMX_ERR_ARG, "gemm: upsample-add epilogue needs G = 1, N %% 8 == 0 and "
                 "M a whole number of %d x %d grids", up->oH, up->oW);
@@ -209,112 +270,52 @@ int gemm_impl(const void* A, const void* A2, const void* B, void* C, const float
     }
     a.nup = up->n; a.uoH = up->oH; a.uoW = up->oW;
   }
-  if (scR > 0) {
-    CMX_REQUIRE(G == 1 || sC > 0, CMX_ERR_ARG, "gemm: scatter");
-    CMX_REQUIRE((!R || lnb) && out_mode == 0 && !ones_col && N == scR * scR * scC && M % (scHo * scWo) == 0,
+  if (p.scR > 0) {
+    CMX_REQUIRE(G == 1 || p.sC > 0, CMX_ERR_ARG, "gemm: scatter");
+    CMX_REQUIRE((!p.R || lnb) && out_mode == 0 && !ones_col && N == p.scR * p.scR * p.scC && M % (p.scHo * p.scWo) == 0,
                 CMX_ERR_ARG, "gemm: patch scatter needs a plain store of N = R*R*C columns");
-    a.scatter = 1; a.scH = scH; a.scW = scW; a.scC = scC; a.scR = scR; a.scHo = scHo; a.scWo = scWo;
+    a.scatter = 1; a.scH = p.scH; a.scW = p.scW; a.scC = p.scC; a.scR = p.scR; a.scHo = p.scHo; a.scWo = p.scWo;
   }
-  const int kstep = fast ? FBK : BK;
-  const int nk = (K + kstep - 1) / kstep;
-  a.kt_per_split = (nk + splitk - 1) / splitk;
-  splitk = (nk + a.kt_per_split - 1) / a.kt_per_split;      // no empty splits
-  a.nsplit = splitk;
+  set_plan(a, L);
   // LayerNorm of C's rows in the same launch (tail = 2): N <= 128, one 64 x 64 / 64 x 128 tile
   // spans the row and the lanes that store it normalise it
-  const bool row_ln = tail != nullptr;
   if (tail) {
     CMX_REQUIRE(fast && N <= 128 && N % 8 == 0 && splitk == 1 && !transA && !transB && out_mode == 0 && !ones_col &&
-                    !a.nup && !a.scatter && gh == 1 && !mask && a.cvec && dtype != 0,
+                    !a.nup && !a.scatter && gh == 1 && !p.mask && a.cvec && dtype != 0,
                 CMX_ERR_ARG, "gemm_ln: the LayerNorm epilogue needs the 16-bit path without split-K, forward layouts, a "
                 "plain aligned store and N <= 128, N %% 8 == 0 (G=%d M=%d N=%d K=%d)", G, M, N, K);
     CMX_REQUIRE(tail->gamma && tail->beta && tail->y && tail->mean && tail->rstd && ((uintptr_t)tail->y & 15) == 0 &&
-                    tail->y != C, CMX_ERR_ARG, "gemm_ln: LayerNorm buffers");
+                    tail->y != p.C, CMX_ERR_ARG, "gemm_ln: LayerNorm buffers");
     a.tail = 2; a.ln_gamma = tail->gamma; a.ln_beta = tail->beta; a.ln_sg = tail->sg; a.ln_y = tail->y;
     a.ln_mean = tail->mean; a.ln_rstd = tail->rstd; a.ln_eps = tail->eps;
   }
   if (lnb) {
-    const bool al = ((uintptr_t)C & 15) == 0 && ((uintptr_t)lnb->x & 15) == 0 && ((uintptr_t)R & 15) == 0 &&
+    const bool al = ((uintptr_t)p.C & 15) == 0 && ((uintptr_t)lnb->x & 15) == 0 && ((uintptr_t)p.R & 15) == 0 &&
                     ((uintptr_t)lnb->dy2 & 15) == 0 && ((uintptr_t)lnb->dxs & 15) == 0;
     // (under the patch scatter a 64 x C tile is one tap of 64 patches: C must be a tile width)
-    const bool rows_ok = a.scatter ? (scC == 64 || scC == 128) && scH == scHo * scR && scW == scWo * scR
+    const bool rows_ok = a.scatter ? (p.scC == 64 || p.scC == 128) && p.scH == p.scHo * p.scR && p.scW == p.scWo * p.scR
                                    : N <= 128 && N % 8 == 0;
-    CMX_REQUIRE(fast && splitk == 1 && !transA && transB && out_mode == 0 && !ones_col && !bias && act == 0 && !mask &&
-                    !a.nup && gh == 1 && !A2 && a.cvec && al && rows_ok && dtype != 0 &&
-                    !tail && lnb->x && lnb->gamma && lnb->mean && lnb->rstd && lnb->part && (!lnb->dxs || rscale),
+    CMX_REQUIRE(fast && splitk == 1 && !transA && transB && out_mode == 0 && !ones_col && !p.bias && p.act == 0 &&
+                    !p.mask && !a.nup && gh == 1 && !p.A2 && a.cvec && al && rows_ok && dtype != 0 &&
+                    !tail && lnb->x && lnb->gamma && lnb->mean && lnb->rstd && lnb->part && (!lnb->dxs || p.rscale),
                 CMX_ERR_ARG, "gemm_ln_bwd: needs the 16-bit dgrad path (transB) without split-K, 16-B aligned rows, "
                 "N <= 128 (N %% 8 == 0), no bias / activation (G=%d M=%d N=%d K=%d)", G, M, N, K);
     a.tail = 3; a.ln_gamma = lnb->gamma; a.ln_sg = lnb->sg; a.ln_mean = const_cast<float*>(lnb->mean); a.ln_rstd = const_cast<float*>(lnb->rstd);
     a.lnb_x = lnb->x; a.lnb_dy2 = lnb->dy2; a.lnb_dxs = lnb->dxs; a.lnb_part = lnb->part;
   }
-  if (plan) {
-    // planning only (cmx_gemm_plan): eligible for a multi launch = the 16-bit path on 64 x 64
-    // tiles, no split-K, no bias-gradient column / upsample / scatter / two-level batch
-    if (!fast || splitk != 1 || ones_col || a.nup || a.scatter || gh != 1 || transA) return 0;
-    int bm, bn;
-    plan_tiles(G, M, nb, K, &bm, &bn);
-    if (bm != 64 || bn != 64) return 0;
-    a.tiles_m = cdiv(M, 64); a.tiles_n = cdiv(nb, 64);
-    memset(plan, 0, sizeof(*plan));
-    plan->a = a; plan->tA = transA; plan->tB = transB; plan->dtype = dtype;
-    plan->nblk = a.tiles_m * a.tiles_n * G;
-    plan->nk64 = (K + FBK - 1) / FBK;
-    return plan->nblk;
+  if (p.plan) {
+    // planning only (cmx_gemm_plan): the block count when eligible for a multi launch, else 0
+    const int nblk = gp::multi_blocks(shape, L);
+    if (!nblk) return 0;
+    a.kt_per_split = (int)gp::cdiv(K, FBK);      // (cmx_gemm_multi sets the k-group's share)
+    memset(p.plan, 0, sizeof(*p.plan));
+    p.plan->a = a; p.plan->tA = transA; p.plan->tB = transB; p.plan->dtype = dtype;
+    p.plan->nblk = nblk;
+    p.plan->nk64 = a.kt_per_split;
+    return nblk;
   }
-  if (fast) {
-    int bm, bn;
-    plan_tiles(G, M, nb, K, &bm, &bn);
-    if (row_ln || lnb) bm = 64, bn = N <= 64 ? 64 : 128;   // one tile spans the row
-    if (lnb && a.scatter) bn = scC;                         // (one tap's C channels)
-    // 64 x 64 tiles that overflow one round of resident blocks by less than CMX_GEMM_MID percent
-    // (5 per CU) take 64 x 128 tiles instead: one round of blocks twice as long, not a second
-    // partial round (0 = off; default 50: GEMM census 1380 -> 1361 us, stage-3 fc1 14.3 -> 13.0 us)
-    static int& mid = cmx_knob("GEMM_MID", 50);
-    if (mid > 0 && bm == 64 && bn == 64 && !row_ln && !lnb && !a.scatter && !a.nup && splitk == 1 && nb >= 128) {
-      const long t64 = (long)cdiv(M, 64) * cdiv(nb, 64) * G, slots = 5L * cu_count();
-      if (t64 > slots && t64 * 100 <= slots * (100 + mid)) bn = 128;
-    }
-    a.tiles_m = cdiv(M, bm); a.tiles_n = cdiv(nb, bn);
-    // tall 64 x 64 problems of at least CMX_GEMM_STREAM tiles (0 = off) and K <= CMX_GEMM_STREAM_K:
-    // the resident streaming grid (gemm_stream_kernel) instead of one block per tile
-    static int& stream_min = cmx_knob("GEMM_STREAM", 1024);
-    static int& stream_k = cmx_knob("GEMM_STREAM_K", 128);
-    const long tiles = (long)a.tiles_m * a.tiles_n * G;
-    if (stream_min > 0 && tiles >= stream_min && K <= stream_k && bm == 64 && bn == 64 && splitk == 1 && !transA && !A2 &&
-        !ones_col && !a.nup && !a.scatter && gh == 1 && !lnb && (!tail || (row_ln && N <= 64))) {
-      if (dtype == 2) launch_stream<f16>(a, G, transB, s);
-      else launch_stream<bf16>(a, G, transB, s);
-    } else {
-      launch_fast(a, bm, bn, G, splitk, transA, transB, dtype, s);
-    }
-  } else {
-    // tile shape: the output's narrow side gets 64 (stage-1 C = 64 outputs, 64-row wgrads)
-    const bool m64 = M <= 64, n64 = N <= 64;
-    a.tiles_m = cdiv(M, m64 ? 64 : 128); a.tiles_n = cdiv(N, n64 ? 64 : 128);
-    if (dtype == 1) {
-      if (m64 && n64) launch_generic<bf16, 64, 64>(a, G, splitk, transA, transB, s);
-      else if (m64) launch_generic<bf16, 64, 128>(a, G, splitk, transA, transB, s);
-      else if (n64) launch_generic<bf16, 128, 64>(a, G, splitk, transA, transB, s);
-      else launch_generic<bf16, 128, 128>(a, G, splitk, transA, transB, s);
-    } else if (dtype == 2) {
-      if (m64 && n64) launch_generic<f16, 64, 64>(a, G, splitk, transA, transB, s);
-      else if (m64) launch_generic<f16, 64, 128>(a, G, splitk, transA, transB, s);
-      else if (n64) launch_generic<f16, 128, 64>(a, G, splitk, transA, transB, s);
-      else launch_generic<f16, 128, 128>(a, G, splitk, transA, transB, s);
-    } else {
-      if (m64 && n64) launch_generic<float, 64, 64>(a, G, splitk, transA, transB, s);
-      else if (m64) launch_generic<float, 64, 128>(a, G, splitk, transA, transB, s);
-      else if (n64) launch_generic<float, 128, 64>(a, G, splitk, transA, transB, s);
-      else launch_generic<float, 128, 128>(a, G, splitk, transA, transB, s);
-    }
-  }
-  if (splitk > 1) {
-    const long work = (long)M * ((nb + 7) / 8) + (ones_col ? M : 0);
-    if (dtype == 1) launch_reduce<bf16>(a, G, work, s);
-    else if (dtype == 2) launch_reduce<f16>(a, G, work, s);
-    else launch_reduce<float>(a, G, work, s);
-  }
-  return cmx_check_launch("gemm");
+  const int st = launch_gemm(L, a, transA, transB, dtype, s);
+  return st != CMX_OK ? st : cmx_check_launch("gemm");
 }
 }  // namespace
 
@@ -325,9 +326,13 @@ int cmx_gemm(const void* A, const void* A2, const void* B, void* C, const float*
              int64_t lda, int64_t lda2, int64_t ldb, int64_t ldc, int64_t sA, int64_t sA2, int64_t sB, int64_t sC,
              int64_t sbias, int64_t sdb, int rows_per_sample, int transA, int transB, int act, int out_mode,
              int ones_col, int splitk, int dtype, hipStream_t s) {
-  return gemm_impl(A, A2, B, C, bias, R, rscale, dbias, workspace, G, M, N, K, K1, lda, lda2, ldb, ldc, sA, sA2, sB,
-                   sC, sbias, sdb, rows_per_sample, transA, transB, act, out_mode, ones_col, splitk, dtype, s, nullptr,
-                   0, 0, 0, 0, 0, 0, 1, 0, 0, 0, nullptr, mask);
+  GemmProblem p;
+  p.A = A; p.A2 = A2; p.B = B; p.C = C; p.bias = bias; p.R = R; p.rscale = rscale; p.mask = mask; p.dbias = dbias;
+  p.workspace = workspace; p.G = G; p.M = M; p.N = N; p.K = K; p.K1 = K1; p.lda = lda; p.lda2 = lda2; p.ldb = ldb;
+  p.ldc = ldc; p.sA = sA; p.sA2 = sA2; p.sB = sB; p.sC = sC; p.sbias = sbias; p.sdb = sdb;
+  p.rows_per_sample = rows_per_sample; p.transA = transA; p.transB = transB; p.act = act; p.out_mode = out_mode;
+  p.ones_col = ones_col; p.splitk = splitk; p.dtype = dtype;
+  return gemm_impl(p, s);
 }
 
 int cmx_gemm_ln(const void* A, const void* A2, const void* B, void* C, const float* bias, const void* R,
@@ -336,21 +341,26 @@ int cmx_gemm_ln(const void* A, const void* A2, const void* B, void* C, const flo
                 int act, const float* ln_gamma, const float* ln_beta, int64_t ln_sg, float ln_eps, void* ln_y,
                 float* ln_mean, float* ln_rstd, int dtype, hipStream_t s) {
   const LnTail t{ln_gamma, ln_beta, (long)ln_sg, ln_y, ln_mean, ln_rstd, ln_eps};
-  return gemm_impl(A, A2, B, C, bias, R, rscale, nullptr, nullptr, G, M, N, K, K1, lda, lda2, ldb, ldc, sA, sA2, sB,
-                   sC, sbias, 0, rows_per_sample, 0, 0, act, 0, 0, 1, dtype, s, nullptr, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0,
-                   nullptr, nullptr, &t);
+  GemmProblem p;
+  p.A = A; p.A2 = A2; p.B = B; p.C = C; p.bias = bias; p.R = R; p.rscale = rscale;
+  p.G = G; p.M = M; p.N = N; p.K = K; p.K1 = K1; p.lda = lda; p.lda2 = lda2; p.ldb = ldb; p.ldc = ldc;
+  p.sA = sA; p.sA2 = sA2; p.sB = sB; p.sC = sC; p.sbias = sbias; p.rows_per_sample = rows_per_sample; p.act = act;
+  p.splitk = 1; p.dtype = dtype; p.tail = &t;
+  return gemm_impl(p, s);
 }
-
 
 int cmx_gemm_ln_bwd(const void* A, const void* B, void* dx, int G, int M, int N, int K, int64_t lda, int64_t ldb,
                     int64_t ldc, int64_t sA, int64_t sB, int64_t sC, const void* x, const float* gamma, int64_t sg,
                     const float* mean, const float* rstd, const void* dres, const void* dy2, const float* sscale,
                     int rows_per_sample, void* dxs, float* partials, int dtype, hipStream_t s) {
   const LnBwd l{x, gamma, (long)sg, mean, rstd, dy2, dxs, partials};
-  return gemm_impl(A, nullptr, B, dx, nullptr, dres, sscale, nullptr, nullptr, G, M, N, K, K, lda, 0, ldb, ldc, sA, 0,
-                   sB, sC, 0, 0, rows_per_sample, 0, 1, 0, 0, 0, 1, dtype, s, nullptr, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0,
-                   nullptr, nullptr, nullptr, &l);
+  GemmProblem p;
+  p.A = A; p.B = B; p.C = dx; p.R = dres; p.rscale = sscale; p.G = G; p.M = M; p.N = N; p.K = K;
+  p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.sA = sA; p.sB = sB; p.sC = sC; p.rows_per_sample = rows_per_sample;
+  p.transB = 1; p.splitk = 1; p.dtype = dtype; p.lnb = &l;
+  return gemm_impl(p, s);
 }
+
 
 size_t cmx_gemm_ln_bwd_partials(int G, int M, int N) { return (size_t)G * ((M + 63) / 64) * 2 * N * sizeof(float); }
 
@@ -366,9 +376,12 @@ int cmx_conv_patch_dgrad_ln_bwd(const void* dy, const void* Wt, void* dx, int G,
               C);
   const int M = NIg * Ho * Wo, Kc = R * R * C;
   const LnBwd l{x, gamma, (long)sg, mean, rstd, dy2, dxs, partials};
-  return gemm_impl(dy, nullptr, Wt, dx, nullptr, dres, sscale, nullptr, nullptr, G, M, Kc, N, N, N, 0, Kc, Kc, sdy, 0,
-                   sW, sdx, 0, 0, rows_per_sample, 0, 1, 0, 0, 0, 1, dtype, s, nullptr, R, H, Wd, C, Ho, Wo, 1, 0, 0, 0,
-                   nullptr, nullptr, nullptr, &l);
+  GemmProblem p;
+  p.A = dy; p.B = Wt; p.C = dx; p.R = dres; p.rscale = sscale; p.G = G; p.M = M; p.N = Kc; p.K = N;
+  p.lda = N; p.ldb = Kc; p.ldc = Kc; p.sA = sdy; p.sB = sW; p.sC = sdx; p.rows_per_sample = rows_per_sample;
+  p.transB = 1; p.splitk = 1; p.dtype = dtype; p.lnb = &l;
+  p.scR = R; p.scH = H; p.scW = Wd; p.scC = C; p.scHo = Ho; p.scWo = Wo;
+  return gemm_impl(p, s);
 }
 
 size_t cmx_conv_patch_dgrad_ln_bwd_partials(int G, int NIg, int Ho, int Wo, int C, int R) {
@@ -386,13 +399,17 @@ int cmx_gemm_plan(void* plan, const void* A, const void* A2, const void* B, void
                   int64_t sbias, int64_t sdb, int rows_per_sample, int transA, int transB, int act, int out_mode,
                   int ones_col, int splitk, int dtype) {
   CMX_REQUIRE(plan, CMX_ERR_ARG, "gemm_plan: null plan");
-  return gemm_impl(A, A2, B, C, bias, R, rscale, dbias, workspace, G, M, N, K, K1, lda, lda2, ldb, ldc, sA, sA2, sB,
-                   sC, sbias, sdb, rows_per_sample, transA, transB, act, out_mode, ones_col, splitk, dtype, nullptr,
-                   nullptr, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, reinterpret_cast<GemmPlan*>(plan), mask);
+  GemmProblem p;
+  p.A = A; p.A2 = A2; p.B = B; p.C = C; p.bias = bias; p.R = R; p.rscale = rscale; p.mask = mask; p.dbias = dbias;
+  p.workspace = workspace; p.G = G; p.M = M; p.N = N; p.K = K; p.K1 = K1; p.lda = lda; p.lda2 = lda2; p.ldb = ldb;
+  p.ldc = ldc; p.sA = sA; p.sA2 = sA2; p.sB = sB; p.sC = sC; p.sbias = sbias; p.sdb = sdb;
+  p.rows_per_sample = rows_per_sample; p.transA = transA; p.transB = transB; p.act = act; p.out_mode = out_mode;
+  p.ones_col = ones_col; p.splitk = splitk; p.dtype = dtype; p.plan = reinterpret_cast<GemmPlan*>(plan);
+  return gemm_impl(p, nullptr);
 }
 
 // n <= 4 planned problems (same dtype and B layout) in ONE launch; waves / ring depth chosen for
-// the combined grid as a single problem's launch would be (launch_bf16_ns)
+// the combined grid as a single problem's launch would be (gemm_plan.h: plan_multi)
 int cmx_gemm_multi(const void* plans, int n, hipStream_t s) {
   CMX_REQUIRE(plans && n >= 1 && n <= MULTI_MAX, CMX_ERR_ARG, "gemm_multi: 1..%d problems (got %d)", MULTI_MAX, n);
   const GemmPlan* pl = reinterpret_cast<const GemmPlan*>(plans);
@@ -409,24 +426,23 @@ int cmx_gemm_multi(const void* plans, int n, hipStream_t s) {
   }
   m.blk0[n] = total;
   for (int i = n + 1; i <= MULTI_MAX; ++i) m.blk0[i] = total;
-  static int& kwk = cmx_knob("GEMM_KW", 2);
-  const bool kw2 = kwk >= 2 && total <= 512 && nk64 >= 4;
-  if (kw2)
-    for (int i = 0; i < n; ++i) m.a[i].kt_per_split = (m.a[i].K + 2 * FBK - 1) / (2 * FBK);
-  const bool ns4 = total <= 256;
+  const gp::GemmLaunch L = gp::plan_multi(total, nk64, gemm_knobs());
+  for (int i = 0; i < n; ++i) m.a[i].kt_per_split = gp::split_k(pl[i].nk64, L.kw).kt;
+  const dim3 grid(L.grid_x), block(L.block);
   const bool tB = pl[0].tB != 0, h = pl[0].dtype == 2;
-#define CMX_MULTI(NS_, KW_, TB_, E_) \
-  hipLaunchKernelGGL((gemm_multi_kernel<NS_, KW_, TB_, E_>), dim3(total), dim3(256 * KW_), 0, s, m)
-#define CMX_MULTI_E(NS_, KW_, TB_) \
-  do { if (h) CMX_MULTI(NS_, KW_, TB_, f16); else CMX_MULTI(NS_, KW_, TB_, bf16); } while (0)
-#define CMX_MULTI_TB(NS_, KW_) do { if (tB) CMX_MULTI_E(NS_, KW_, true); else CMX_MULTI_E(NS_, KW_, false); } while (0)
-  if (kw2 && ns4) CMX_MULTI_TB(4, 2);
-  else if (kw2) CMX_MULTI_TB(2, 2);
-  else if (ns4) CMX_MULTI_TB(4, 1);
-  else CMX_MULTI_TB(2, 1);
-#undef CMX_MULTI_TB
-#undef CMX_MULTI_E
-#undef CMX_MULTI
+  bool ok = false;
+#define CMX_GEMM_MULTI(NS, KW, TB, H, E)                                                       \
+  if (L.ns == NS && L.kw == KW && tB == TB && h == H) {                                        \
+    hipLaunchKernelGGL((gemm_multi_kernel<NS, KW, TB, E>), grid, block, 0, s, m);               \
+    ok = true;                                                                                  \
+  }
+#define CMX_GEMM_MULTI_W(NS, KW) \
+  CMX_GEMM_MULTI(NS, KW, false, false, bf16) CMX_GEMM_MULTI(NS, KW, true, false, bf16) \
+  CMX_GEMM_MULTI(NS, KW, false, true, f16) CMX_GEMM_MULTI(NS, KW, true, true, f16)
+  CMX_GEMM_MULTI_W(4, 2) CMX_GEMM_MULTI_W(2, 2) CMX_GEMM_MULTI_W(4, 1) CMX_GEMM_MULTI_W(2, 1)
+#undef CMX_GEMM_MULTI_W
+#undef CMX_GEMM_MULTI
+  CMX_REQUIRE(ok, CMX_ERR_LAUNCH, "gemm_multi: no kernel for NS %d, KW %d", L.ns, L.kw);
   return cmx_check_launch("gemm_multi");
 }
 
@@ -442,9 +458,11 @@ int cmx_gemm_multi(const void* plans, int n, hipStream_t s) {
 int cmx_gemm_h2(const void* A, const void* B, void* C, float* workspace, int G, int gh, int M, int N, int K,
                 int64_t lda, int64_t ldb, int64_t ldc, int64_t sA, int64_t sAh, int64_t sB, int64_t sBh, int64_t sC,
                 int64_t sCh, int transA, int transB, int out_mode, int splitk, int dtype, hipStream_t s) {
-  return gemm_impl(A, nullptr, B, C, nullptr, nullptr, nullptr, nullptr, workspace, G, M, N, K, K, lda, 0, ldb, ldc, sA,
-                   0, sB, sC, 0, 0, 1, transA, transB, 0, out_mode, 0, splitk, dtype, s, nullptr, 0, 0, 0, 0, 0, 0, gh,
-                   sAh, sBh, sCh);
+  GemmProblem p;
+  p.A = A; p.B = B; p.C = C; p.workspace = workspace; p.G = G; p.M = M; p.N = N; p.K = K;
+  p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.sA = sA; p.sB = sB; p.sC = sC; p.transA = transA; p.transB = transB;
+  p.out_mode = out_mode; p.splitk = splitk; p.dtype = dtype; p.gh = gh; p.sAh = sAh; p.sBh = sBh; p.sCh = sCh;
+  return gemm_impl(p, s);
 }
 
 int cmx_conv_patch_dgrad(const void* dy, const void* Wt, void* dx, int G, int NIg, int H, int Wd, int C, int R, int Ho,
@@ -452,8 +470,11 @@ int cmx_conv_patch_dgrad(const void* dy, const void* Wt, void* dx, int G, int NI
   CMX_REQUIRE(G > 0 && NIg > 0 && C % 8 == 0 && R > 0 && Ho == H / R && Wo == Wd / R && Ho > 0 && Wo > 0, CMX_ERR_SHAPE,
               "conv_patch_dgrad: H=%d W=%d R=%d Ho=%d Wo=%d C=%d", H, Wd, R, Ho, Wo, C);
   const int M = NIg * Ho * Wo, Kc = R * R * C;
-  return gemm_impl(dy, nullptr, Wt, dx, nullptr, nullptr, nullptr, nullptr, nullptr, G, M, Kc, N, N, N, 0, Kc, Kc, sdy,
-                   0, sW, sdx, 0, 0, 1, 0, 1, 0, 0, 0, 1, dtype, s, nullptr, R, H, Wd, C, Ho, Wo);
+  GemmProblem p;
+  p.A = dy; p.B = Wt; p.C = dx; p.G = G; p.M = M; p.N = Kc; p.K = N; p.lda = N; p.ldb = Kc; p.ldc = Kc;
+  p.sA = sdy; p.sB = sW; p.sC = sdx; p.transB = 1; p.splitk = 1; p.dtype = dtype;
+  p.scR = R; p.scH = H; p.scW = Wd; p.scC = C; p.scHo = Ho; p.scWo = Wo;
+  return gemm_impl(p, s);
 }
 
 // DecoderHead.linear_fuse on the restructured decoder (MLPDecoder.py:66-77):
@@ -478,8 +499,10 @@ int cmx_decoder_fuse_fwd(const void* e1, const void* Wf_c1, void* Z, const float
   }
   up.oH = H1; up.oW = W1;
   const int M = B * H1 * W1;
-  return gemm_impl(e1, nullptr, Wf_c1, Z, bias, nullptr, nullptr, nullptr, nullptr, 1, M, E, K, K, lda, 0, ldw, E, 0, 0,
-                   0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, dtype, s, &up);
+  GemmProblem p;
+  p.A = e1; p.B = Wf_c1; p.C = Z; p.bias = bias; p.G = 1; p.M = M; p.N = E; p.K = K; p.lda = lda; p.ldb = ldw;
+  p.ldc = E; p.splitk = 1; p.dtype = dtype; p.up = &up;
+  return gemm_impl(p, s);
 }
 
 
@@ -490,14 +513,7 @@ size_t cmx_gemm_group_record_size(void) { return sizeof(GroupRec); }
 // split only bounds the k-loop of one block (<= 48 k-tiles of 64 = 3072 tokens per block)
 int cmx_gemm_grouped_splitk(int G, int M, int N, int K, int ones_col) {
   if (G <= 0 || M <= 0 || N <= 0 || K <= 0) return 1;
-  // <= 48 k-tiles of 64 tokens per block (CMX_GROUPED_KT): measured against 16 / 24 / 32 / 64
-  // on the B2 step (interleaved A/B: 32 -> 48 is +1.5 %, 64 no better; fewer slabs to reduce)
-  static int& kt = cmx_knob("GROUPED_KT", 48);
-  const int nk = (K + FBK - 1) / FBK;
-  int s = (nk + kt - 1) / kt;
-  if (s > 64) s = 64;
-  const int per = (nk + s - 1) / s;
-  return (nk + per - 1) / per;
+  return gp::grouped_split(K, gemm_knobs());
 }
 
 int cmx_gemm_group_pack(void* rec, const void* A, const void* B, void* C, float* dbias, float* workspace, int G, int M,
@@ -510,8 +526,9 @@ int cmx_gemm_group_pack(void* rec, const void* A, const void* B, void* C, float*
   CMX_REQUIRE((long)M * N < (1L << 31), CMX_ERR_SHAPE, "gemm_group_pack: problem too large");
   CMX_REQUIRE(fast_ok(A, nullptr, B, M, N, K, K, lda, 0, ldb, sA, 0, sB, transA, transB, ones_col), CMX_ERR_ARG,
               "gemm_group_pack: operands not eligible for the bf16 LDS-DMA path");
-  if (splitk <= 0) splitk = cmx_gemm_grouped_splitk(G, M, N, K, ones_col);
-  CMX_REQUIRE(splitk == 1 || workspace, CMX_ERR_ARG, "gemm_group_pack: split-K needs a workspace");
+  const int nb = ones_col ? N - 1 : N;
+  const gp::GemmLaunch L = gp::plan_grouped(G, M, nb, K, splitk, gemm_knobs());
+  CMX_REQUIRE((splitk > 0 ? splitk : L.nsplit) == 1 || workspace, CMX_ERR_ARG, "gemm_group_pack: split-K needs a workspace");
   GroupRec r{};
   GemmArgs& a = r.a;
   a.A = A; a.A2 = nullptr; a.B = B; a.C = C; a.dbias = dbias; a.ws = workspace;
@@ -519,14 +536,10 @@ int cmx_gemm_group_pack(void* rec, const void* A, const void* B, void* C, float*
   a.act = 0; a.out_mode = out_mode; a.ones_col = ones_col; a.vec = 1;
   a.cvec = ((uintptr_t)C % 16 == 0) && (ldc * 4) % 16 == 0 && (sC * 4) % 16 == 0;
   a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.sA = sA; a.sB = sB; a.sC = sC; a.sdb = sdb;
-  const int nk = (K + FBK - 1) / FBK;
-  a.kt_per_split = (nk + splitk - 1) / splitk;
-  a.nsplit = (nk + a.kt_per_split - 1) / a.kt_per_split;
-  const int nb = ones_col ? N - 1 : N;
-  r.bm = tile_dim(M); r.bn = tile_dim(nb);
-  a.tiles_m = cdiv(M, r.bm); a.tiles_n = cdiv(nb, r.bn);
+  set_plan(a, L);
+  r.bm = L.bm; r.bn = L.bn;
   r.blk0 = blk0;
-  r.nblk = a.tiles_m * a.tiles_n * G * a.nsplit;
+  r.nblk = (int)L.grid_x;
   memcpy(rec, &r, sizeof(r));
   return r.nblk;
 }
@@ -546,8 +559,9 @@ int cmx_gemm_group_pack_conv_wgrad(void* rec, const void* dy, const void* x, flo
               "gemm_group_pack_conv_wgrad: too large for 31-bit offsets");
   const int ones = dbias ? 1 : 0;
   const int Nk = C + ones;                      // output columns (+ bias-gradient column)
-  if (splitk <= 0) splitk = cmx_gemm_grouped_splitk(G, N, Nk, M, ones);
-  CMX_REQUIRE(splitk == 1 || workspace, CMX_ERR_ARG, "gemm_group_pack_conv_wgrad: split-K needs a workspace");
+  const gp::GemmLaunch L = gp::plan_grouped(G, N, C, M, splitk, gemm_knobs());
+  CMX_REQUIRE((splitk > 0 ? splitk : L.nsplit) == 1 || workspace, CMX_ERR_ARG,
+              "gemm_group_pack_conv_wgrad: split-K needs a workspace");
   GroupRec r{};
   GemmArgs& a = r.a;
   a.A = dy; a.B = x; a.C = dW + (long)tap * C; a.dbias = dbias; a.ws = workspace;
@@ -557,13 +571,10 @@ int cmx_gemm_group_pack_conv_wgrad(void* rec, const void* dy, const void* x, flo
   a.cvec = (((uintptr_t)a.C % 16) == 0) && (a.ldc * 4) % 16 == 0 && (sdW * 4) % 16 == 0;
   a.conv = 2; a.cH = H; a.cW = Wd; a.cC = C; a.cKW = KW; a.cst = stride; a.cpad = pad; a.cHo = Ho; a.cWo = Wo;
   a.ctap = tap;
-  const int nk = (M + FBK - 1) / FBK;
-  a.kt_per_split = (nk + splitk - 1) / splitk;
-  a.nsplit = (nk + a.kt_per_split - 1) / a.kt_per_split;
-  r.bm = tile_dim(N); r.bn = tile_dim(C);
-  a.tiles_m = cdiv(N, r.bm); a.tiles_n = cdiv(C, r.bn);
+  set_plan(a, L);
+  r.bm = L.bm; r.bn = L.bn;
   r.blk0 = blk0;
-  r.nblk = a.tiles_m * a.tiles_n * G * a.nsplit;
+  r.nblk = (int)L.grid_x;
   memcpy(rec, &r, sizeof(r));
   return r.nblk;
 }
@@ -589,22 +600,15 @@ int cmx_conv_implicit_fwd(const void* x, const void* Wt, void* y, const float* b
   a.conv = 1; a.cH = H; a.cW = Wd; a.cC = C; a.cKW = KW; a.cst = stride; a.cpad = pad; a.cHo = Ho; a.cWo = Wo;
   // the SR conv has few output pixels and a long K (stage 1: 600 x 64 x 4096): split K like a
   // plain GEMM (splitk <= 0: the library's choice, cmx_gemm_splitk(G, M, N, K, 0, 1))
-  if (splitk <= 0) splitk = auto_split(G, (int)M, N, (int)K, 0);
-  CMX_REQUIRE(splitk == 1 || workspace, CMX_ERR_ARG, "conv_implicit_fwd: split-K needs a workspace");
+  gp::GemmShape shape;
+  shape.G = G; shape.M = (int)M; shape.N = N; shape.K = (int)K; shape.dtype = dtype; shape.fast = 1;
+  shape.splitk = splitk; shape.tile_only = 1;
+  const gp::GemmLaunch L = gp::plan_gemm(shape, gemm_knobs(), cu_count());
+  CMX_REQUIRE((splitk > 0 ? splitk : L.nsplit) == 1 || workspace, CMX_ERR_ARG, "conv_implicit_fwd: split-K needs a workspace");
   a.ws = workspace;
-  const int nk = (int)((K + FBK - 1) / FBK);
-  a.kt_per_split = (nk + splitk - 1) / splitk;
-  splitk = (nk + a.kt_per_split - 1) / a.kt_per_split;
-  a.nsplit = splitk;
-  int bm, bn;
-  plan_tiles(G, (int)M, N, (int)K, &bm, &bn);
-  a.tiles_m = cdiv(M, bm); a.tiles_n = cdiv(N, bn);
-  launch_fast(a, bm, bn, G, splitk, 0, 0, dtype, s);
-  if (splitk > 1) {
-    if (dtype == 2) launch_reduce<f16>(a, G, (long)M * ((N + 7) / 8), s);
-    else launch_reduce<bf16>(a, G, (long)M * ((N + 7) / 8), s);
-  }
-  return cmx_check_launch("conv_implicit_fwd");
+  set_plan(a, L);
+  const int st = launch_gemm(L, a, 0, 0, dtype, s);
+  return st != CMX_OK ? st : cmx_check_launch("conv_implicit_fwd");
 }
 
 int cmx_gemm_grouped(const void* recs, int nrec, int total_blocks, int dtype, hipStream_t s) {

@@ -3,14 +3,16 @@
 // units: gemm_fast_bf16.hip / gemm_fast_f16.hip (the 16-bit LDS-DMA tile kernels),
 // gemm_generic_*.hip (the register-staged path per element type), gemm.hip (entry points,
 // grouped launches).  Launchers instantiated elsewhere are declared `extern template` in the
-// TUs that call them (GEMM_EXTERN_LAUNCHERS below).
+// TU that calls them (gemm.hip).  The launch policy is gemm_plan.h.
 #pragma once
 #include "cmx_mfma.h"
 #include "cmx_dma.h"
+#include "gemm_plan.h"
 #include <string.h>
 #include <stdlib.h>
 
 namespace gemmk {
+using gemmplan::GemmLaunch;
 
 struct GemmArgs {
   const void* A; const void* A2; const void* B; void* C; const float* bias; const void* R; const float* rscale;
@@ -1157,17 +1159,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs p) {
   else if (p.ones_col && e < work + p.M) dbias_store(p, g, (int)(e - work), v[0]);
 }
 
+// ============================================================================ host side
+// Which kernel, tile, waves, split and grid a problem gets is decided in gemm_plan.h (no HIP in
+// there); the launchers below only map a gemmplan::GemmLaunch to the instantiation it names and
+// answer false when there is none.
 template <typename T>
-void launch_reduce(const GemmArgs& a, int G, long groups, hipStream_t s) {
-  if (a.nsplit >= 32) hipLaunchKernelGGL((splitk_reduce_kernel<T, 16>), dim3(cdiv(groups, 16), G), dim3(256), 0, s, a);
-  else if (a.nsplit >= 8) hipLaunchKernelGGL((splitk_reduce_kernel<T, 4>), dim3(cdiv(groups, 64), G), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((splitk_reduce_kernel<T, 1>), dim3(cdiv(groups, 256), G), dim3(256), 0, s, a);
+void launch_reduce(const GemmLaunch& L, const GemmArgs& a, hipStream_t s) {
+  const dim3 grid(L.red_grid_x, L.red_grid_y);
+  if (L.red_zl == 16) hipLaunchKernelGGL((splitk_reduce_kernel<T, 16>), grid, dim3(256), 0, s, a);
+  else if (L.red_zl == 4) hipLaunchKernelGGL((splitk_reduce_kernel<T, 4>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((splitk_reduce_kernel<T, 1>), grid, dim3(256), 0, s, a);
 }
 
-// ============================================================================ host side
-template <int BM, int BN, int NS, int KW = 1, typename E = bf16>
-void launch_bf16(const GemmArgs& a, int G, int nsplit, int tA, int tB, hipStream_t s) {
-  dim3 grid(a.tiles_m * a.tiles_n * G * nsplit);
+template <int BM, int BN, int NS, int KW, typename E>
+void launch_tile_as(const GemmArgs& a, dim3 grid, int tA, int tB, hipStream_t s) {
   if constexpr (BM == 64 && (BN == 64 || (BN == 128 && KW == 1))) {
     if (a.tail == 2) {                // whole-row LayerNorm in the epilogue (forward layouts, tiles_n = 1)
       hipLaunchKernelGGL((gemm_bf16_kernel<64, BN, false, false, NS, KW, E, 2>), grid, dim3(256 * KW), 0, s, a);
@@ -1186,47 +1191,23 @@ void launch_bf16(const GemmArgs& a, int G, int nsplit, int tA, int tB, hipStream
 #undef CMX_GEMM_LAUNCH
 }
 
-template <int BM, int BN, typename E = bf16>
-void launch_bf16_ns(const GemmArgs& a, int G, int nsplit, int tA, int tB, hipStream_t s) {
-  const long blocks = (long)a.tiles_m * a.tiles_n * G * nsplit;
-  // k-group blocks for 64 x 64 tiles without split-K or bias column (CMX_GEMM_KW = the largest
-  // group count allowed, default 2; 1 = off).  Measured (scripts/gemm_sweep.py, G2 M600 N512):
-  // K 2048 20.1 -> 11.9 us, K 512 7.5 -> 5.8 us at KW = 2; grids above 512 blocks and one-slot
-  // problems are slower with it (M9600 N128 K512: 9.7 -> 10.4 us), so they keep 4 waves.
-  static int& kw = cmx_knob("GEMM_KW", 2);
-  if constexpr (BM == 64 && BN == 64) {
-    const int nk64 = (a.K + FBK - 1) / FBK;
-    if (kw >= 2 && nsplit == 1 && !a.ones_col && blocks <= 512 && nk64 >= 4) {
-      GemmArgs b = a;
-      if (kw >= 4 && blocks <= 256 && nk64 >= 16) {
-        b.kt_per_split = (b.K + 4 * FBK - 1) / (4 * FBK);
-        launch_bf16<64, 64, 2, 4, E>(b, G, nsplit, tA, tB, s);
-        return;
-      }
-      b.kt_per_split = (b.K + 2 * FBK - 1) / (2 * FBK);
-      if (blocks <= 256) launch_bf16<64, 64, 4, 2, E>(b, G, nsplit, tA, tB, s);
-      else launch_bf16<64, 64, 2, 2, E>(b, G, nsplit, tA, tB, s);
-      return;
-    }
-  }
-  if (blocks <= 256) launch_bf16<BM, BN, 4, 1, E>(a, G, nsplit, tA, tB, s);
-  else launch_bf16<BM, BN, 2, 1, E>(a, G, nsplit, tA, tB, s);
-}
-
-// the 16-bit fast path for one problem: tile shape (bm, bn), element type from dtype (1 bf16, 2 fp16)
+// the 16-bit tile kernels (one block per tile and split): every (tile, NS, KW) the plan can name;
+// k-group waves (KW > 1) exist for 64 x 64 tiles only
 template <typename E>
-void launch_fast_t(const GemmArgs& a, int bm, int bn, int G, int nsplit, int tA, int tB, hipStream_t s) {
-  if (bm == 64 && bn == 64) launch_bf16_ns<64, 64, E>(a, G, nsplit, tA, tB, s);
-  else if (bm == 64) launch_bf16_ns<64, 128, E>(a, G, nsplit, tA, tB, s);
-  else if (bn == 64) launch_bf16_ns<128, 64, E>(a, G, nsplit, tA, tB, s);
-  else launch_bf16_ns<128, 128, E>(a, G, nsplit, tA, tB, s);
-}
-inline void launch_fast(const GemmArgs& a, int bm, int bn, int G, int nsplit, int tA, int tB, int dtype, hipStream_t s) {
-  if (dtype == 2) launch_fast_t<f16>(a, bm, bn, G, nsplit, tA, tB, s);
-  else launch_fast_t<bf16>(a, bm, bn, G, nsplit, tA, tB, s);
+bool launch_tile(const GemmLaunch& L, const GemmArgs& a, int tA, int tB, hipStream_t s) {
+#define CMX_GEMM_TILE(BM, BN, NS, KW)                                   \
+  if (L.bm == BM && L.bn == BN && L.ns == NS && L.kw == KW) {           \
+    launch_tile_as<BM, BN, NS, KW, E>(a, dim3(L.grid_x), tA, tB, s);    \
+    return true;                                                        \
+  }
+  CMX_GEMM_TILE(64, 64, 2, 4) CMX_GEMM_TILE(64, 64, 4, 2) CMX_GEMM_TILE(64, 64, 2, 2)
+  CMX_GEMM_TILE(64, 64, 4, 1) CMX_GEMM_TILE(64, 64, 2, 1) CMX_GEMM_TILE(64, 128, 4, 1) CMX_GEMM_TILE(64, 128, 2, 1)
+  CMX_GEMM_TILE(128, 64, 4, 1) CMX_GEMM_TILE(128, 64, 2, 1) CMX_GEMM_TILE(128, 128, 4, 1) CMX_GEMM_TILE(128, 128, 2, 1)
+#undef CMX_GEMM_TILE
+  return false;
 }
 
-// one block per CU (queried once)
+// CUs of the current device (queried once)
 inline int cu_count() {
   static const int n = [] {
     int dev = 0, c = 0;
@@ -1239,36 +1220,32 @@ inline int cu_count() {
 }
 
 template <typename E>
-void launch_stream(const GemmArgs& a, int G, int tB, hipStream_t s) {
-  const long total = (long)a.tiles_m * a.tiles_n * G;
-  static int& bpc = cmx_knob("GEMM_STREAM_BPC", CMX_STREAM_LB);   // resident blocks per CU (VGPR-bound)
-  long grid = (long)(bpc > 0 && bpc <= CMX_STREAM_LB ? bpc : CMX_STREAM_LB) * cu_count();
-  if (grid > total) grid = total;
-  grid = (grid + 7) / 8 * 8;
-  if (a.tail == 2) {
-    hipLaunchKernelGGL((gemm_stream_kernel<false, E, 2>), dim3((unsigned)grid), dim3(256), 0, s, a);
-  } else if (tB) {
-    hipLaunchKernelGGL((gemm_stream_kernel<true, E, 0>), dim3((unsigned)grid), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((gemm_stream_kernel<false, E, 0>), dim3((unsigned)grid), dim3(256), 0, s, a);
+void launch_stream(const GemmLaunch& L, const GemmArgs& a, int tB, hipStream_t s) {
+  const dim3 grid(L.grid_x);
+  if (a.tail == 2) hipLaunchKernelGGL((gemm_stream_kernel<false, E, 2>), grid, dim3(256), 0, s, a);
+  else if (tB) hipLaunchKernelGGL((gemm_stream_kernel<true, E, 0>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((gemm_stream_kernel<false, E, 0>), grid, dim3(256), 0, s, a);
+}
+
+// the register-staged kernels: tile x layouts x (EXT: upsample-add / scatter epilogue)
+template <typename T>
+bool launch_generic(const GemmLaunch& L, const GemmArgs& a, int tA, int tB, hipStream_t s) {
+  const dim3 grid(L.grid_x, L.grid_y, L.grid_z);
+  const bool ext = a.nup || a.scatter;
+#define CMX_GEMM_GENERIC(BM, BN, TA, TB, EXT)                                                             \
+  if (L.bm == BM && L.bn == BN && !tA == !TA && !tB == !TB && ext == EXT) {                               \
+    hipLaunchKernelGGL((gemm_generic_kernel<T, BM, BN, TA, TB, EXT>), grid, dim3(256), 0, s, a);          \
+    return true;                                                                                          \
   }
-}
-
-template <typename T, int BM, int BN, bool EXT>
-void launch_generic_x(const GemmArgs& a, int G, int nsplit, int tA, int tB, hipStream_t s) {
-  dim3 grid(a.tiles_m * a.tiles_n, G, nsplit);
-#define CMX_GEMM_LAUNCH(TA, TB) hipLaunchKernelGGL((gemm_generic_kernel<T, BM, BN, TA, TB, EXT>), grid, dim3(256), 0, s, a)
-  if (!tA && !tB) CMX_GEMM_LAUNCH(false, false);
-  else if (!tA && tB) CMX_GEMM_LAUNCH(false, true);
-  else if (tA && tB) CMX_GEMM_LAUNCH(true, true);
-  else CMX_GEMM_LAUNCH(true, false);
-#undef CMX_GEMM_LAUNCH
-}
-
-template <typename T, int BM, int BN>
-void launch_generic(const GemmArgs& a, int G, int nsplit, int tA, int tB, hipStream_t s) {
-  if (a.nup || a.scatter) launch_generic_x<T, BM, BN, true>(a, G, nsplit, tA, tB, s);
-  else launch_generic_x<T, BM, BN, false>(a, G, nsplit, tA, tB, s);
+#define CMX_GEMM_GENERIC_TILE(BM, BN)                                                                      \
+  CMX_GEMM_GENERIC(BM, BN, false, false, false) CMX_GEMM_GENERIC(BM, BN, false, true, false)              \
+  CMX_GEMM_GENERIC(BM, BN, true, true, false) CMX_GEMM_GENERIC(BM, BN, true, false, false)                \
+  CMX_GEMM_GENERIC(BM, BN, false, false, true) CMX_GEMM_GENERIC(BM, BN, false, true, true)                \
+  CMX_GEMM_GENERIC(BM, BN, true, true, true) CMX_GEMM_GENERIC(BM, BN, true, false, true)
+  CMX_GEMM_GENERIC_TILE(64, 64) CMX_GEMM_GENERIC_TILE(64, 128) CMX_GEMM_GENERIC_TILE(128, 64) CMX_GEMM_GENERIC_TILE(128, 128)
+#undef CMX_GEMM_GENERIC_TILE
+#undef CMX_GEMM_GENERIC
+  return false;
 }
 
 // the bf16 fast path needs every operand row to be whole 16-B chunks on 16-B boundaries
@@ -1292,77 +1269,11 @@ inline bool fast_ok(const void* A, const void* A2, const void* B, int M, int N, 
   return extA < lim && extB < lim && extA2 < lim;
 }
 
-inline int tile_dim(int n) { return n <= 64 ? 64 : 128; }
-
-// Tile policy of the bf16 path (CMX_GEMM_TILES=0 restores the 128-wide-first policy, for A/B
-// measurements).  Policy 1: when 128-wide tiles leave the chip under-filled (< 400 tiles),
-// take 64 x 64 tiles -- 4x the tiles, a lighter per-block k-loop and no split-K combine --
-// and split K only when even those leave it under-filled.
-inline int tile_policy() {
-  static int& p = cmx_knob("GEMM_TILES", 1);
-  return p;
-}
-
-// Small-K policy (CMX_GEMM_SMALLK=k, default 256): problems with K <= k take 64 x 64 tiles
-// whatever their tile count -- a block of one to four k-tiles is a latency chain (DMA, MFMA,
-// epilogue), and the 128 x 128 tile's 67 KB epilogue image allows only two such chains per CU
-// where 64 x 64 blocks (32 KB) run four or more.  Measured on the B2 step's GEMM census
-// (profiles/r02_r_gemm_census.txt): the stage-1/2 MLP and decoder-input GEMMs
-// (M 38400 / 9600, K 64-256) gain 10-25 % each, 2558 -> 2485 us per step at k = 640; the one
-// 512 x 512 decoder GEMM (K 512) is the shape that keeps 128-wide tiles faster, hence 256.
-// A narrow output (N <= 64, K 512: the decoder's class / c1 products) also takes 64 x 64.
-inline int smallk_policy() {
-  static int& p = cmx_knob("GEMM_SMALLK", 256);
-  return p;
-}
-
-inline void plan_tiles(int G, int M, int nb, int K, int* bm, int* bn) {
-  *bm = tile_dim(M);
-  *bn = tile_dim(nb);
-  if (tile_policy() == 1) {
-    // (CMX_GEMM_T128, default 400: the stage-3 MLP GEMMs, 380 128-wide tiles, run 64 x 64;
-    // measured +0.6 % per step over 240 in interleaved A/B)
-    static int& t128min = cmx_knob("GEMM_T128", 400);
-    const long t128 = (long)cdiv(M, *bm) * cdiv(nb, *bn) * G;
-    if (t128 < t128min) *bm = *bn = 64;
-  }
-  if (K <= smallk_policy() || (nb <= 64 && smallk_policy() > 0)) *bm = *bn = 64;
-}
-
-// split factor for the bf16 path: one block per CU when the output has few tiles (each split
-// keeps >= 4 k-tiles of 64; the slabs cost 8 B of HBM traffic per output element and split)
-inline int auto_split(int G, int M, int N, int K, int ones_col) {
-  const int nb = ones_col ? N - 1 : N;
-  int bm, bn;
-  plan_tiles(G, M, nb, K, &bm, &bn);
-  const long tiles = (long)cdiv(M, bm) * cdiv(nb, bn) * G;
-  const int nk = (K + FBK - 1) / FBK;
-  const long full = tile_policy() == 1 ? 128 : 200;
-  if (tiles >= full || nk < 8) return 1;
-  // an under-filled 64 x 64 problem without a bias-gradient column runs as k-group blocks
-  // (launch_bf16_ns, KW waves per tile) instead of split-K slabs + a reducer launch: measured
-  // +1.2 % per step (interleaved A/B, 246.7 / 247.1 -> 249.5 / 250.5 img/s; CMX_GEMM_SPLITKW=0
-  // restores split-K)
-  static int& splitkw = cmx_knob("GEMM_SPLITKW", 1);
-  // (short k-loops only: a k-group block walks nk / 2 ring slots serially, and the FFM context
-  // products -- 64 x 64 over 19200 tokens, nk = 300 -- keep split-K: 10.8 vs 33 us)
-  if (splitkw && bm == 64 && bn == 64 && !ones_col && nk <= 32) return 1;
-  long s = (256 + tiles - 1) / tiles;
-  s = s < nk / 4 ? s : nk / 4;
-  if (s > 128) s = 128;
-  if (s < 1) s = 1;
-  const int per = (nk + (int)s - 1) / (int)s;
-  return (nk + per - 1) / per;
-}
-
 }  // namespace gemmk
 
-#define CMX_GEMM_GENERIC_SHAPES(X, T) X(T, 64, 64) X(T, 64, 128) X(T, 128, 64) X(T, 128, 128)
-#define CMX_GEMM_GENERIC_INST(T, BM, BN) \
-  template void gemmk::launch_generic<T, BM, BN>(const GemmArgs&, int, int, int, int, hipStream_t);
-#define CMX_GEMM_GENERIC_EXTERN(T, BM, BN) \
-  extern template void gemmk::launch_generic<T, BM, BN>(const GemmArgs&, int, int, int, int, hipStream_t);
-#define CMX_GEMM_FAST_INST(E)                                                                         \
-  template void gemmk::launch_fast_t<E>(const GemmArgs&, int, int, int, int, int, int, hipStream_t);
-#define CMX_GEMM_FAST_EXTERN(E)                                                                              \
-  extern template void gemmk::launch_fast_t<E>(const GemmArgs&, int, int, int, int, int, int, hipStream_t);
+// explicit instantiations of the launchers: gemm_fast_*.hip / gemm_generic_*.hip hold one each, so
+// the kernels compile in parallel; gemm.hip declares them extern
+#define CMX_GEMM_GENERIC_INST(T) \
+  template bool gemmk::launch_generic<T>(const gemmk::GemmLaunch&, const gemmk::GemmArgs&, int, int, hipStream_t);
+#define CMX_GEMM_FAST_INST(E) \
+  template bool gemmk::launch_tile<E>(const gemmk::GemmLaunch&, const gemmk::GemmArgs&, int, int, hipStream_t);
