@@ -56,8 +56,9 @@ def test_gemm_layouts(dev, dtype, G, M, N, K, tA, tB):
 @pytest.mark.parametrize("res", [False, True])
 @pytest.mark.parametrize("K", [96, 2048])
 def test_gemm_epilogues(dev, dtype, act, res, K):
-    """K = 2048 on a 600 x 192 output takes the auto split-K path: the epilogue then runs in
-    the slab reducer."""
+    """K = 2048 on a 600 x 192 output is an under-filled 64 x 64 problem with a short k-loop: it runs
+    as KW = 2 k-group blocks (GEMM_SPLITKW), no split-K and no reducer, and the epilogue runs in the
+    tile kernel.  The reducer's epilogue is covered by tests/test_gpu_gemm_exact.py (red_* cases)."""
     torch.manual_seed(1)
     from rgbx_semantic_segmentation_amd import kernels as Kn
     G, M, N, rps = 2, 600, 192, 300
@@ -77,7 +78,8 @@ def test_gemm_epilogues(dev, dtype, act, res, K):
 def test_gemm_relu_mask_epilogue(dev, dtype, K, res):
     """ReLU-backward mask epilogue (CrossPath's channel_proj ReLU, net_utils.py:273-274):
     C = (R + A B^T) * [mask > 0], in place over a column half of a wider buffer (the FFM's
-    [dy | du] gradient), through the tile path and (K = 2048) the split-K reducer."""
+    [dy | du] gradient), through the tile path; K = 2048 runs as KW = 2 k-group blocks (no split-K,
+    no reducer: the reducer's mask epilogue is covered by tests/test_gpu_gemm_exact.py)."""
     torch.manual_seed(9)
     from rgbx_semantic_segmentation_amd import kernels as Kn
     G, M, N = 2, 600, 96
