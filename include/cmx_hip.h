@@ -34,13 +34,13 @@ typedef struct ihipStream_t* hipStream_t;
  * from, and the Python binding refuses a library whose revision differs (an older .so with the
  * same symbol names but shifted arguments would otherwise corrupt memory silently).  Bump it
  * on every change of an entry point's argument list. */
-#define CMX_ABI_VERSION 6
+#define CMX_ABI_VERSION 7
 int cmx_abi_version(void);
 const char* cmx_last_error(void);
 /* pinned host -> device copy of a packed record table on `stream` (see grouped launches) */
 int cmx_upload(void* dst, const void* src, size_t nbytes, hipStream_t stream);
 /* launch-policy knobs (GEMM_TILES, GEMM_SMALLK, GEMM_T128, GEMM_KW, GEMM_SPLITKW, SRA_SMALL_N,
- * SRA_DKV_DIRECT, SRA_QW, SRA_NW, GROUPED_KT, GROUPED_CHUNK): initialised from the
+ * SRA_SMALL_FWD_N, SRA_DQ_SEQ, SRA_DKV_DIRECT, SRA_QW, SRA_NW, GROUPED_KT, GROUPED_CHUNK): initialised from the
  * CMX_<NAME> environment variable, changed in-process by cmx_tune for interleaved A/B runs;
  * a knob set before the first launch that reads it keeps the set value.  tune_get: -1 if unset. */
 int cmx_tune(const char* name, int value);
@@ -86,6 +86,13 @@ int cmx_colsum(const void* x, float* out, float* workspace, int64_t M, int G, in
 int cmx_sra_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk, int heads, int D, int64_t qs, int64_t kvs, int64_t os, float scale, int dtype, hipStream_t stream);
 size_t cmx_sra_attn_bwd_workspace(int Bt, int N, int Nk, int heads, int D);
 int cmx_sra_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq, void* dk, void* dv, float* workspace, int Bt, int N, int Nk, int heads, int D, int64_t qs, int64_t kvs, int64_t os, int64_t dos, int64_t dqs, int64_t dkvs, float scale, int dtype, hipStream_t stream);
+/* The launch decision cmx_sra_attn_fwd / cmx_sra_attn_bwd take for this problem under the current knobs
+ * (SRA_SMALL_N, SRA_SMALL_FWD_N, SRA_DQ_SEQ, SRA_QW, SRA_NW, SRA_DKV_DIRECT) and the device's CU count;
+ * launches nothing.  out[0..8) (n >= 8): forward path, backward path (0 general / 1 fast / 2 small), QW, NW of
+ * the fast forward / dQ (0 when neither is fast), dK / dV query chunks, dK / dV written directly (no slabs, no
+ * reduce launch), short-sequence dQ form (1 sra_dq_small_seq / 0 sra_dq_small), CU count.  aligned: bit 0 =
+ * q, k, v, o, dO, dq start on 16 B with row strides % 8 == 0, bit 1 = the same for dK / dV. */
+int cmx_sra_plan(int* out, int n, int Bt, int N, int Nk, int heads, int D, int dtype, int aligned);
 
 /* ---- depthwise 3x3 + bias + act: Mix-FFN DWConv + GELU (dual_segformer.py:27-33,67-71) and
  *      ChannelEmbed DW3x3 + ReLU (net_utils.py:315-318).  h,out: (NI, H, W, C) NHWC,

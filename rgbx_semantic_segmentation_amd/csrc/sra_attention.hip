@@ -24,6 +24,7 @@
 //          bit-reproducible).
 // MFMA FLOPs per (b, head): fwd 4*N*Nk*D, bwd 8*N*Nk*D (+ S recompute 2*N*Nk*D).
 #include "cmx_mfma.h"
+#include "sra_plan.h"
 
 namespace {
 
@@ -420,15 +421,7 @@ __global__ __launch_bounds__(256) void sra_dkv_reduce_kernel(const float* __rest
   }
 }
 
-int bwd_nchunk(int Bt, int N, int Nk, int heads) {
-  const int nkb = (Nk + BK - 1) / BK;
-  const long base = (long)Bt * heads * nkb;
-  long nc = (512 + base - 1) / base;
-  const long maxc = (N + KT - 1) / KT;
-  if (nc > maxc) nc = maxc;
-  if (nc < 1) nc = 1;
-  return (int)nc;
-}
+static_assert(sraplan::GEN_BK == BK && sraplan::GEN_KT == KT, "sra_plan.h and the general kernels disagree on a tile");
 int bwd_qc(int N, int nchunk) {
   int qc = (N + nchunk - 1) / nchunk;
   return (qc + KT - 1) / KT * KT;
@@ -436,31 +429,40 @@ int bwd_qc(int N, int nchunk) {
 
 }  // namespace
 
-// sra_fast.hip: LDS-resident K/V path for bf16 / fp16, D = 64
-bool sra_fast_ok(int D, int Nk, int dtype, const void* const* ptrs, int nptr, const long* strides, int nstr);
-bool sra_fast_fwd_ok(int D, int Nk, int dtype, const void* const* ptrs, int nptr, const long* strides, int nstr);
+// sra_fast.hip: LDS-resident K/V kernels for bf16 / fp16, D = 64 (any Nk: keys stream through LDS
+// in 320-key chunks) and their short-sequence forms (Nk <= 320).  sra_plan_now is the launch
+// decision (sra_plan.h) under the live knobs; the launchers below take its fields.
+sraplan::SraPlan sra_plan_now(int Bt, int N, int Nk, int heads, int D, int dtype, int aligned);
+int sra_dkv_fast_chunks(int Bt, int N, int Nk, int heads);
 void sra_fwd_fast_launch(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
-                         int heads, long qs, long kvs, long os, float sl2, int dtype, hipStream_t s);
+                         int heads, long qs, long kvs, long os, float sl2, int qw, int nw, int dtype, hipStream_t s);
 void sra_dq_fast_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
                         const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                        long os, long dos, long dqs, float sl2, float scale, int dtype, hipStream_t s);
-int sra_dkv_fast_chunks(int Bt, int N, int Nk, int heads);
+                        long os, long dos, long dqs, float sl2, float scale, int qw, int nw, int dtype,
+                        hipStream_t s);
 void sra_dkv_fast_launch(const void* q, const void* k, const void* v, const void* dout, const float* lse,
                          const float* Dws, float* ws_dk, float* ws_dv, void* dk, void* dv, long dkvs, int Bt, int N,
                          int Nk, int heads, long qs,
                          long kvs, long dos, int nchunk, float sl2, float scale, int dtype, hipStream_t s);
-
-bool sra_small_ok(int D, int N, int Nk, int dtype, const void* const* ptrs, int nptr, const long* strides, int nstr);
-bool sra_small_fwd_ok(int D, int N, int Nk, int dtype, const void* const* ptrs, int nptr, const long* strides,
-                      int nstr);
 void sra_fwd_small_launch(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
                           int heads, long qs, long kvs, long os, float sl2, int dtype, hipStream_t s);
 void sra_dq_small_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
                          const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                         long os, long dos, long dqs, float sl2, float scale, int dtype, hipStream_t s);
+                         long os, long dos, long dqs, float sl2, float scale, int seq, int dtype, hipStream_t s);
 void sra_dkv_small_launch(const void* q, const void* k, const void* v, const void* dout, const float* lse,
                           const float* Dws, void* dk, void* dv, long dkvs, int Bt, int N, int Nk, int heads, long qs,
                           long kvs, long dos, float sl2, float scale, int dtype, hipStream_t s);
+
+namespace {
+// 16-B aligned starts and row strides of whole 16-B groups (`aligned` of plan_sra)
+bool rows16(const void* const* ptrs, int nptr, const long* strides, int nstr) {
+  for (int i = 0; i < nptr; ++i)
+    if (ptrs[i] && ((uintptr_t)ptrs[i] & 15)) return false;
+  for (int i = 0; i < nstr; ++i)
+    if (strides[i] % 8) return false;
+  return true;
+}
+}  // namespace
 
 #define SRA_D_DISPATCH(D, ...)                                              \
   do {                                                                      \
@@ -478,17 +480,16 @@ int cmx_sra_attn_fwd(const void* q, const void* k, const void* v, void* o, float
   CMX_REQUIRE(Bt > 0 && N > 0 && Nk > 0 && heads > 0, CMX_ERR_SHAPE, "sra_fwd: bad shape");
   CMX_REQUIRE(qs % 8 == 0 && kvs % 8 == 0 && os % 8 == 0, CMX_ERR_SHAPE, "sra_fwd: strides %% 8");
   const float sl2 = scale * 1.4426950408889634f;
-  {
-    const void* ptrs[] = {q, k, v, o};
-    const long strides[] = {qs, kvs, os};
-    if (sra_small_fwd_ok(D, N, Nk, dtype, ptrs, 4, strides, 3)) {
-      sra_fwd_small_launch(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, dtype, s);
-      return cmx_check_launch("sra_fwd");
-    }
-    if (sra_fast_fwd_ok(D, Nk, dtype, ptrs, 4, strides, 3)) {
-      sra_fwd_fast_launch(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, dtype, s);
-      return cmx_check_launch("sra_fwd");
-    }
+  const void* ptrs[] = {q, k, v, o};
+  const long strides[] = {qs, kvs, os};
+  const sraplan::SraPlan plan = sra_plan_now(Bt, N, Nk, heads, D, dtype, rows16(ptrs, 4, strides, 3) ? 1 : 0);
+  if (plan.fwd == sraplan::SRA_SMALL) {
+    sra_fwd_small_launch(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, dtype, s);
+    return cmx_check_launch("sra_fwd");
+  }
+  if (plan.fwd == sraplan::SRA_FAST) {
+    sra_fwd_fast_launch(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, plan.qw, plan.nw, dtype, s);
+    return cmx_check_launch("sra_fwd");
   }
   const dim3 grid(cdiv(N, BQ), heads, Bt);
   SRA_D_DISPATCH(D, CMX_DISPATCH(dtype, T, {
@@ -499,7 +500,7 @@ int cmx_sra_attn_fwd(const void* q, const void* k, const void* v, void* o, float
 }
 
 size_t cmx_sra_attn_bwd_workspace(int Bt, int N, int Nk, int heads, int D) {
-  int nc = bwd_nchunk(Bt, N, Nk, heads);
+  int nc = sraplan::general_dkv_chunks(Bt, N, Nk, heads);
   const int ncf = sra_dkv_fast_chunks(Bt, N, Nk, heads);   // the bf16 fast path may take either
   if (ncf > nc) nc = ncf;
   const size_t slab = (size_t)nc * Bt * heads * Nk * D;
@@ -516,25 +517,28 @@ int cmx_sra_attn_bwd(const void* q, const void* k, const void* v, const void* o,
   const float sl2 = scale * 1.4426950408889634f;
   const void* ptrs[] = {q, k, v, o, dout, dq};
   const long strides[] = {qs, kvs, os, dos, dqs};
-  if (sra_small_ok(D, N, Nk, dtype, ptrs, 6, strides, 5) && ((uintptr_t)dk & 15) == 0 && ((uintptr_t)dv & 15) == 0 &&
-      dkvs % 8 == 0) {
+  const void* gptrs[] = {dk, dv};
+  const int aligned = (rows16(ptrs, 6, strides, 5) ? 1 : 0) | (rows16(gptrs, 2, &dkvs, 1) ? 2 : 0);
+  const sraplan::SraPlan plan = sra_plan_now(Bt, N, Nk, heads, D, dtype, aligned);
+  if (plan.bwd == sraplan::SRA_SMALL) {
     // short sequences: keys split over waves (dQ), query tiles over waves (dK / dV), no slabs
     float* Dws = workspace;
-    sra_dq_small_launch(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, dtype, s);
+    sra_dq_small_launch(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale,
+                        plan.dq_seq, dtype, s);
     sra_dkv_small_launch(q, k, v, dout, lse, Dws, dk, dv, dkvs, Bt, N, Nk, heads, qs, kvs, dos, sl2, scale, dtype, s);
     return cmx_check_launch("sra_bwd");
   }
   // fast path for any Nk: dQ streams K / V in LDS-sized chunks, dK / dV splits keys over workgroups
-  const bool fast = sra_fast_fwd_ok(D, Nk, dtype, ptrs, 6, strides, 5);
-  const bool fast_dq = fast;
-  const int nc = fast ? sra_dkv_fast_chunks(Bt, N, Nk, heads) : bwd_nchunk(Bt, N, Nk, heads);
+  const bool fast = plan.bwd == sraplan::SRA_FAST;
+  const int nc = plan.dkv_chunks;
   const int qc = bwd_qc(N, nc);
   float* Dws = workspace;
   float* ws_dk = Dws + (size_t)Bt * heads * N;
   float* ws_dv = ws_dk + (size_t)nc * Bt * heads * Nk * D;
   SRA_D_DISPATCH(D, CMX_DISPATCH(dtype, T, {
-    if (fast_dq)
-      sra_dq_fast_launch(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, dtype, s);
+    if (fast)
+      sra_dq_fast_launch(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, plan.qw,
+                         plan.nw, dtype, s);
     else
       hipLaunchKernelGGL((sra_bwd_dq_kernel<T, DD>), dim3(cdiv(N, BQ), heads, Bt), dim3(256), 0, s,
                          (const T*)q, (const T*)k, (const T*)v, (const T*)o, (const T*)dout, lse, Dws,
@@ -547,11 +551,27 @@ int cmx_sra_attn_bwd(const void* q, const void* k, const void* v, const void* o,
                          (const T*)q, (const T*)k, (const T*)v, (const T*)dout, lse, Dws, ws_dk, ws_dv, Bt,
                          N, Nk, heads, qs, kvs, dos, qc, nc, sl2, scale);
     const long total = (long)Bt * heads * Nk * D;     // D % 4 == 0: 4-wide groups never straddle a row
-    if (!(fast && nc == 1))                           // one chunk: the fast kernel wrote dK / dV
+    if (!plan.dkv_direct)                             // one chunk: the fast kernel wrote dK / dV
     hipLaunchKernelGGL((sra_dkv_reduce_kernel<T>), dim3(cdiv(total / 4, 64)), dim3(256), 0, s, ws_dk, ws_dv, (T*)dk,
                        (T*)dv, Bt, Nk, heads, D, dkvs, nc);
   }));
   return cmx_check_launch("sra_bwd");
+}
+
+// The launch decision of cmx_sra_attn_fwd / cmx_sra_attn_bwd for a problem under the current knobs; launches
+// nothing.  out[0..n): fwd path, bwd path (0 general / 1 fast / 2 small), qw, nw, dK / dV chunks, dK / dV
+// direct, dq-seq, CU count (sraplan::SraPlan).  aligned: bit 0 = q, k, v, o, dO, dq rows on 16 B, bit 1 = dK / dV.
+int cmx_sra_plan(int* out, int n, int Bt, int N, int Nk, int heads, int D, int dtype, int aligned) {
+  CMX_REQUIRE(out && n >= sraplan::SRA_PLAN_INTS, CMX_ERR_ARG, "sra_plan: out holds %d ints, the plan has %d", n,
+              sraplan::SRA_PLAN_INTS);
+  CMX_REQUIRE(Bt > 0 && N > 0 && Nk > 0 && heads > 0, CMX_ERR_SHAPE, "sra_plan: bad shape");
+  CMX_REQUIRE(D == 32 || D == 64, CMX_ERR_SHAPE, "sra: head dim %d unsupported", D);
+  CMX_REQUIRE(dtype >= 0 && dtype <= 2, CMX_ERR_DTYPE, "sra_plan: dtype %d", dtype);
+  const sraplan::SraPlan plan = sra_plan_now(Bt, N, Nk, heads, D, dtype, aligned);
+  const int f[sraplan::SRA_PLAN_INTS] = {plan.fwd, plan.bwd,        plan.qw,     plan.nw,
+                                         plan.dkv_chunks, plan.dkv_direct, plan.dq_seq, plan.cus};
+  for (int i = 0; i < sraplan::SRA_PLAN_INTS; ++i) out[i] = f[i];
+  return CMX_OK;
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 // cross-half shuffle; each wave owns QW 32-query sub-tiles for MFMA/VALU overlap.
 #include "cmx_mfma.h"
 #include "cmx_dma.h"
+#include "sra_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -1043,23 +1044,7 @@ __global__ __launch_bounds__(64 * SQW) void sra_dkv_small(const E* __restrict__ 
   }
 }
 
-int pick_qw(int N, int heads, int Bt) {
-  static int& force = cmx_knob("SRA_QW", 0);     // 1 / 2: query sub-tiles per wave (A/B), 0 = auto
-  if (force == 1 || force == 2) return force;
-  const long wg2 = (long)cdiv(N, 64 * NWAVE) * heads * Bt;   // workgroups at 2 sub-tiles per wave
-  return wg2 >= 512 ? 2 : 1;
-}
-
-
-// waves per workgroup: 8 (two per SIMD share one K/V image) unless that leaves fewer than
-// 128 workgroups (stage 3: 100, stage 4: 64 at B2 480x640), where 2-wave workgroups spread
-// the work over 2.5-4x more CUs (measured: dQ 17.7 -> 14.8 us at stages 3 and 4; 4-wave
-// workgroups at stage 2 (152 -> 304) were slower, 13.8 -> 16.4 us forward).  Every workgroup
-// stages the (b, head)'s K / V (L2-resident after the first): only L2 -> LDS traffic.
-// 10 waves when the 8-wave grid overflows one workgroup per CU and the 10-wave grid does not
-// (stage 1 of B2 480 x 640: 300 -> 240 workgroups; measured fwd 19.6 -> 15.9 us, bwd 69.2 ->
-// 61.6 us; the 44 CUs that ran a second 8-wave workgroup set the launch time.  At stage 2 the
-// 8-wave grid already fits, and 10 waves were slower: 11.7 -> 14.2 us forward)
+// CU count of the current device (pick_nw, sra_plan.h); 256 when it cannot be read
 int sra_cus() {
   static const int n = [] {
     int dev = 0, c = 0;
@@ -1071,44 +1056,46 @@ int sra_cus() {
   return n;
 }
 
-int pick_nw(int N, int heads, int Bt, int qw) {
-  static int& force = cmx_knob("SRA_NW", 0);     // 2 / 4 / 8 / 10 waves per workgroup (A/B), 0 = auto
-  if (force == 2 || force == 4 || force == 8) return qw == 2 && force == 2 ? 4 : force;
-  if (force == 10 && qw == 1) return 10;
-  if (qw == 1 && (long)cdiv(N, 32 * NWAVE) * heads * Bt > sra_cus() && (long)cdiv(N, 320) * heads * Bt <= sra_cus())
-    return 10;
-  if (qw == 2 || (long)cdiv(N, 32 * NWAVE) * heads * Bt >= 128) return NWAVE;
-  return 2;
+// the tile constants plan_sra counts with are the kernels'
+static_assert(sraplan::HD == HD && sraplan::NKP_MAX == NKP_MAX && sraplan::NWAVE == NWAVE && sraplan::QT == QT,
+              "sra_plan.h and sra_fast.hip disagree on a tile constant");
+
+// knobs are read when a launch is planned (eager call or graph capture)
+sraplan::SraKnobs sra_knobs() {
+  static const sraplan::SraKnobs def;            // the defaults live in sra_plan.h
+  static int& small_n = cmx_knob("SRA_SMALL_N", def.small_n);
+  static int& small_fwd_n = cmx_knob("SRA_SMALL_FWD_N", def.small_fwd_n);
+  static int& dq_seq = cmx_knob("SRA_DQ_SEQ", def.dq_seq);
+  static int& qw = cmx_knob("SRA_QW", def.qw);
+  static int& nw = cmx_knob("SRA_NW", def.nw);
+  static int& dkv_direct = cmx_knob("SRA_DKV_DIRECT", def.dkv_direct);
+  sraplan::SraKnobs k;
+  k.small_n = small_n;
+  k.small_fwd_n = small_fwd_n;
+  k.dq_seq = dq_seq;
+  k.qw = qw;
+  k.nw = nw;
+  k.dkv_direct = dkv_direct;
+  return k;
 }
 
 }  // namespace
 
-// the forward streams keys through LDS in NKP_MAX-key chunks: any Nk (bf16 / fp16, D = 64, 16-B rows)
-bool sra_fast_fwd_ok(int D, int Nk, int dtype, const void* const* ptrs, int nptr, const long* strides, int nstr) {
-  if ((dtype != 1 && dtype != 2) || D != HD || Nk <= 0) return false;
-  for (int i = 0; i < nptr; ++i)
-    if (ptrs[i] && ((uintptr_t)ptrs[i] & 15)) return false;
-  for (int i = 0; i < nstr; ++i)
-    if (strides[i] % 8) return false;
-  return true;
+// the one launch decision of the SRA family (rules: sra_plan.h) under the live knobs and CU count;
+// cmx_sra_attn_fwd / cmx_sra_attn_bwd launch from it and cmx_sra_plan reports it
+sraplan::SraPlan sra_plan_now(int Bt, int N, int Nk, int heads, int D, int dtype, int aligned) {
+  return sraplan::plan_sra(Bt, N, Nk, heads, D, dtype, aligned, sra_knobs(), sra_cus());
 }
 
-// bf16 / fp16, D = 64, Nk <= 320, 16-B aligned rows: the LDS-resident path (sra_attention.hip calls these)
-bool sra_fast_ok(int D, int Nk, int dtype, const void* const* ptrs, int nptr, const long* strides, int nstr) {
-  if ((dtype != 1 && dtype != 2) || D != HD || Nk > NKP_MAX || Nk <= 0) return false;
-  for (int i = 0; i < nptr; ++i)
-    if (ptrs[i] && ((uintptr_t)ptrs[i] & 15)) return false;
-  for (int i = 0; i < nstr; ++i)
-    if (strides[i] % 8) return false;
-  return true;
+// fast dK / dV query chunks under the live knobs (workspace sizing)
+int sra_dkv_fast_chunks(int Bt, int N, int Nk, int heads) {
+  return sraplan::fast_dkv_chunks(Bt, N, Nk, heads, sra_knobs());
 }
 
 template <typename E>
 void sra_fwd_fast_launch_t(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
-                           int heads, long qs, long kvs, long os, float sl2, hipStream_t s) {
+                           int heads, long qs, long kvs, long os, float sl2, int qw, int nw, hipStream_t s) {
   const int nkp = (Nk + KTILE - 1) / KTILE * KTILE;
-  const int qw = pick_qw(N, heads, Bt);
-  const int nw = pick_nw(N, heads, Bt, qw);
   const dim3 grid(cdiv(N, 32 * nw * qw), heads, Bt);
 #define CMX_SRA_FWD(QW_, NW_)                                                                                       \
   hipLaunchKernelGGL((sra_fwd_fast<E, QW_, NW_>), grid, dim3(64 * NW_), 0, s, (const E*)q, (const E*)k,         \
@@ -1118,18 +1105,15 @@ void sra_fwd_fast_launch_t(const void* q, const void* k, const void* v, void* o,
   else if (nw == 10) CMX_SRA_FWD(1, 10);
   else if (nw == 8) CMX_SRA_FWD(1, 8);
   else if (nw == 4) CMX_SRA_FWD(1, 4);
-  else if (nw == 2) CMX_SRA_FWD(1, 2);
-  else CMX_SRA_FWD(1, 1);
+  else CMX_SRA_FWD(1, 2);                        // pick_nw returns 2, 4, 8 or 10
 #undef CMX_SRA_FWD
 }
 
 template <typename E>
 void sra_dq_fast_launch_t(const void* q, const void* k, const void* v, const void* o, const void* dout,
                           const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                          long os, long dos, long dqs, float sl2, float scale, hipStream_t s) {
+                          long os, long dos, long dqs, float sl2, float scale, int qw, int nw, hipStream_t s) {
   const int nkp = (Nk + KTILE - 1) / KTILE * KTILE;
-  const int qw = pick_qw(N, heads, Bt);
-  const int nw = pick_nw(N, heads, Bt, qw);
   const dim3 grid(cdiv(N, 32 * nw * qw), heads, Bt);
 #define CMX_SRA_DQ(QW_, NW_)                                                                                        \
   hipLaunchKernelGGL((sra_dq_fast<E, QW_, NW_>), grid, dim3(64 * NW_), 0, s, (const E*)q, (const E*)k,          \
@@ -1140,28 +1124,12 @@ void sra_dq_fast_launch_t(const void* q, const void* k, const void* v, const voi
   else if (nw == 10) CMX_SRA_DQ(1, 10);
   else if (nw == 8) CMX_SRA_DQ(1, 8);
   else if (nw == 4) CMX_SRA_DQ(1, 4);
-  else if (nw == 2) CMX_SRA_DQ(1, 2);
-  else CMX_SRA_DQ(1, 1);
+  else CMX_SRA_DQ(1, 2);                         // pick_nw returns 2, 4, 8 or 10
 #undef CMX_SRA_DQ
 }
 
-// partial dK / dV slabs of the query chunks (layout of sra_attention.hip's generic path)
-int sra_dkv_fast_chunks(int Bt, int N, int Nk, int heads) {
-  // query chunks per (image, head, 320-key chunk): ~one workgroup per CU over the whole grid
-  // (the SRA layers have one key chunk; IFFM's full cross attention has Nk / 320 of them,
-  // which already fill the chip, and every extra query chunk is another Nk x D slab to reduce)
-  const long base = (long)Bt * heads * ((Nk + NKP_MAX - 1) / NKP_MAX);
-  // short query sequences: one chunk, the gradients written directly (no fp32 slabs, no
-  // reduce launch); CMX_SRA_DKV_DIRECT = the largest N that takes it
-  static int& direct_n = cmx_knob("SRA_DKV_DIRECT", 0);
-  if (N <= direct_n) return 1;
-  long nc = (256 + base - 1) / base;
-  const long maxc = (N + QT - 1) / QT;
-  if (nc > maxc) nc = maxc;
-  if (nc > 64) nc = 64;
-  return (int)(nc < 1 ? 1 : nc);
-}
-
+// partial dK / dV slabs of the query chunks (layout of sra_attention.hip's generic path); nchunk == 1:
+// the gradients themselves
 template <typename E>
 void sra_dkv_fast_launch_t(const void* q, const void* k, const void* v, const void* dout, const float* lse,
                            const float* Dws, float* ws_dk, float* ws_dv, void* dk, void* dv, long dkvs, int Bt, int N,
@@ -1176,20 +1144,23 @@ void sra_dkv_fast_launch_t(const void* q, const void* k, const void* v, const vo
                      Nk, heads, qs, kvs, dos, qc, nchunk, sl2, scale);
 }
 
-// dtype 1 = bf16, 2 = fp16 (the callers checked sra_fast_fwd_ok)
+// dtype 1 = bf16, 2 = fp16 (the plan said SRA_FAST); qw, nw: the plan's
 void sra_fwd_fast_launch(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
-                         int heads, long qs, long kvs, long os, float sl2, int dtype, hipStream_t s) {
-  if (dtype == 2) sra_fwd_fast_launch_t<f16>(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, s);
-  else sra_fwd_fast_launch_t<bf16>(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, s);
+                         int heads, long qs, long kvs, long os, float sl2, int qw, int nw, int dtype, hipStream_t s) {
+  if (dtype == 2) sra_fwd_fast_launch_t<f16>(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, qw, nw, s);
+  else sra_fwd_fast_launch_t<bf16>(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, qw, nw, s);
 }
 
 void sra_dq_fast_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
                         const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                        long os, long dos, long dqs, float sl2, float scale, int dtype, hipStream_t s) {
+                        long os, long dos, long dqs, float sl2, float scale, int qw, int nw, int dtype,
+                        hipStream_t s) {
   if (dtype == 2)
-    sra_dq_fast_launch_t<f16>(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, s);
+    sra_dq_fast_launch_t<f16>(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, qw,
+                              nw, s);
   else
-    sra_dq_fast_launch_t<bf16>(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, s);
+    sra_dq_fast_launch_t<bf16>(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, qw,
+                               nw, s);
 }
 
 void sra_dkv_fast_launch(const void* q, const void* k, const void* v, const void* dout, const float* lse,
@@ -1205,26 +1176,15 @@ void sra_dkv_fast_launch(const void* q, const void* k, const void* v, const void
 }
 
 // ---------------------------------------------------------------- short sequences (sra_*_small)
-// eligible: 16-bit storage, D = 64, Nk <= 320 (one 64-key tile per wave), 16-B aligned rows, and a
-// short query sequence (N <= CMX_SRA_SMALL_N, default 2048: stages 3 / 4 of B2 / B4)
-bool sra_small_ok(int D, int N, int Nk, int dtype, const void* const* ptrs, int nptr, const long* strides, int nstr) {
-  static int& small_n = cmx_knob("SRA_SMALL_N", 2048);
-  return N <= small_n && sra_fast_ok(D, Nk, dtype, ptrs, nptr, strides, nstr);
-}
-
-// the forward takes the short-sequence kernel only up to CMX_SRA_SMALL_FWD_N queries (default 600:
+// eligible (sra_plan.h): 16-bit storage, D = 64, Nk <= 320 (one 64-key tile per wave), 16-B aligned
+// rows, and a short query sequence (N <= CMX_SRA_SMALL_N, default 2048: stages 3 / 4 of B2 / B4).
+// The forward takes the short-sequence kernel only up to CMX_SRA_SMALL_FWD_N queries (default 600:
 // stage 4; stage 3's N = 1200 runs the general LDS-resident forward).  Measured standalone
 // (profiles/r05_e_sra_standalone.txt, Bt = 4, Nk = 300): N = 1200 x 5 heads 16.0 us small vs 11.9 us
 // fast; N = 300 x 8 heads 9.0 vs 10.6 us.  Both forwards sit at the same error against fp64 at the
 // B2 / B4 stage-3 / 4 shapes (tests/test_gpu_kernels.py::test_sra_fwd_kernel_choice); the round-5
 // config-4 trip (FRMs.3.channel_weights.mlp.0.bias ratio 18.4) was the parity test's ReLU-band cap,
 // which now excludes exactly the rows whose ReLU decision flipped
-bool sra_small_fwd_ok(int D, int N, int Nk, int dtype, const void* const* ptrs, int nptr, const long* strides,
-                      int nstr) {
-  static int& small_fwd_n = cmx_knob("SRA_SMALL_FWD_N", 600);
-  return N <= small_fwd_n && sra_small_ok(D, N, Nk, dtype, ptrs, nptr, strides, nstr);
-}
-
 void sra_fwd_small_launch(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
                           int heads, long qs, long kvs, long os, float sl2, int dtype, hipStream_t s) {
   const dim3 grid(cdiv(N, 64), heads, Bt), block(64 * cdiv(Nk, KTILE));
@@ -1238,9 +1198,9 @@ void sra_fwd_small_launch(const void* q, const void* k, const void* v, void* o, 
 
 void sra_dq_small_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
                          const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                         long os, long dos, long dqs, float sl2, float scale, int dtype, hipStream_t s) {
+                         long os, long dos, long dqs, float sl2, float scale, int seq, int dtype, hipStream_t s) {
   const dim3 grid(cdiv(N, 64), heads, Bt), block(64 * cdiv(Nk, KTILE));
-  static int& seq = cmx_knob("SRA_DQ_SEQ", 1);      // sra_dq_small_seq (0: sra_dq_small)
+  // seq (CMX_SRA_DQ_SEQ, default 1): sra_dq_small_seq (0: sra_dq_small)
 #define CMX_SRA_DQS(E_)                                                                                            \
   if (seq) hipLaunchKernelGGL((sra_dq_small_seq<E_, 2>), grid, block, 0, s, (const E_*)q, (const E_*)k,            \
                               (const E_*)v, (const E_*)o, (const E_*)dout, lse, Dws, (E_*)dq, N, Nk, heads, qs, kvs, \

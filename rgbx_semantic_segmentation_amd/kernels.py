@@ -6,6 +6,7 @@ Activations are token-major and contiguous unless a stride argument says otherwi
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import torch
@@ -307,6 +308,24 @@ def gemm_h2(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, out_mode: int = 0
 
 
 # ------------------------------------------------------------------------------ SRA attention
+SRA_PATHS = ("general", "fast", "small")
+SraPlan = collections.namedtuple("SraPlan", "fwd bwd qw nw dkv_chunks dkv_direct dq_seq cus")
+
+
+def sra_plan(Bt, N, Nk, heads, D, dtype, aligned=True) -> SraPlan:
+    """The launch decision sra_attn_fwd / sra_attn_bwd take for this problem under the current knobs
+    (cmx_sra_plan; nothing is launched).  fwd / bwd: "general", "fast" or "small"; (qw, nw): the
+    instantiation of the fast forward / dQ (0 when neither is fast); dkv_chunks: query chunks of the
+    dK / dV kernel; dkv_direct: it stores dK / dV itself (no fp32 slabs, no reduce launch); dq_seq: the
+    short-sequence dQ form; cus: the CU count used.  aligned: every row on 16 B (False: none; an int is
+    passed through, bit 0 = q, k, v, o, dO, dq and bit 1 = dK / dV)."""
+    code = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[dtype]
+    out = (ctypes.c_int32 * 8)()
+    call("cmx_sra_plan", ctypes.addressof(out), 8, Bt, N, Nk, heads, D, code, 3 if aligned is True else int(aligned))
+    f = list(out)
+    return SraPlan(SRA_PATHS[f[0]], SRA_PATHS[f[1]], f[2], f[3], f[4], bool(f[5]), bool(f[6]), f[7])
+
+
 def sra_attn_fwd(q, k, v, Bt, N, Nk, heads, D, scale, qs, kvs, save_lse=True):
     """q: base pointer tensor of (Bt, N, *) rows with stride qs; k/v: views into the kv
     projection (k = kv[..., :C], v = kv[..., C:]) with row stride kvs."""
