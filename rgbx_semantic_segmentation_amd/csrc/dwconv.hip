@@ -446,31 +446,78 @@ __global__ __launch_bounds__(256) void dw2_fwd_kernel(const T* __restrict__ h, c
     bias[0] = bias[1] = pk_splat(0.f);
   }
   const T* hc = hs + cq * 4;
-  for (int it = pl; it < TY2 * TX2; it += PPI) {
-    const int r = it / TX2, c = it % TX2;
-    const int y = t.ty0 + r, x = t.tx0 + c;
-    if (y >= H || x >= W) continue;
-    cmx_f2 acc[2] = {bias[0], bias[1]};
+  if constexpr (PPI == TX2) {
+    // A thread's pixels are rows 0 .. TY2-1 of ONE tile column (c = pl): the 3 x 3 window of
+    // unpacked taps slides down it in registers.  Each row fetches and unpacks only its three
+    // new bottom taps; the rows rotate by renaming, the loop being fully unrolled.  Every
+    // output keeps the tap order of the loop below.
+    const int x = t.tx0 + pl;
+    const int nr = H - t.ty0;                       // rows of this tile inside the image (block-uniform)
+    if (x >= W) return;                             // no barrier after this point
+    const T* hp = hc + pl * CB;
+    cmx_f2 win[3][3][2];                            // [image row % 3][column c .. c+2][pair]
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        cmx_f2 v[2];
-        v4_unpack<T>(v4_load<T>(hc + ((r + i) * EX + c + j) * CB), v);
-        const int tap = FLIP ? 8 - (i * 3 + j) : i * 3 + j;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) acc[u] = pk_fma(wr[u][tap], v[u], acc[u]);
-      }
-    const long o = ibase + ((long)y * W + x) * C + cq * 4;
-    if (gprime) {              // act'(z), saved so the backward needs no conv recompute
-      cmx_f2 gd[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) gd[u] = act2_grad<ACT>(acc[u]);
-      v4_store<T>(gprime + o, gd);
+    for (int j = 0; j < 3; ++j) {
+      v4_unpack<T>(v4_load<T>(hp + j * CB), win[0][j]);
+      v4_unpack<T>(v4_load<T>(hp + (EX + j) * CB), win[1][j]);
     }
+    long o = ibase + ((long)t.ty0 * W + x) * C + cq * 4;
+    const long ostep = (long)W * C;
 #pragma unroll
-    for (int u = 0; u < 2; ++u) acc[u] = act2_fwd<ACT>(acc[u]);
-    v4_store<T>(out + o, acc);
+    for (int r = 0; r < TY2; ++r) {
+      if (r < nr) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          v4_unpack<T>(v4_load<T>(hp + ((r + 2) * EX + j) * CB), win[(r + 2) % 3][j]);
+        }
+        cmx_f2 acc[2] = {bias[0], bias[1]};
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const int tap = FLIP ? 8 - (i * 3 + j) : i * 3 + j;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) acc[u] = pk_fma(wr[u][tap], win[(r + i) % 3][j][u], acc[u]);
+          }
+        if (gprime) {            // act'(z), saved so the backward needs no conv recompute
+          cmx_f2 gd[2];
+#pragma unroll
+          for (int u = 0; u < 2; ++u) gd[u] = act2_grad<ACT>(acc[u]);
+          v4_store<T>(gprime + o, gd);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) acc[u] = act2_fwd<ACT>(acc[u]);
+        v4_store<T>(out + o, acc);
+        o += ostep;
+      }
+    }
+  } else {
+    for (int it = pl; it < TY2 * TX2; it += PPI) {
+      const int r = it / TX2, c = it % TX2;
+      const int y = t.ty0 + r, x = t.tx0 + c;
+      if (y >= H || x >= W) continue;
+      cmx_f2 acc[2] = {bias[0], bias[1]};
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          cmx_f2 v[2];
+          v4_unpack<T>(v4_load<T>(hc + ((r + i) * EX + c + j) * CB), v);
+          const int tap = FLIP ? 8 - (i * 3 + j) : i * 3 + j;
+#pragma unroll
+          for (int u = 0; u < 2; ++u) acc[u] = pk_fma(wr[u][tap], v[u], acc[u]);
+        }
+      const long o = ibase + ((long)y * W + x) * C + cq * 4;
+      if (gprime) {              // act'(z), saved so the backward needs no conv recompute
+        cmx_f2 gd[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) gd[u] = act2_grad<ACT>(acc[u]);
+        v4_store<T>(gprime + o, gd);
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) acc[u] = act2_fwd<ACT>(acc[u]);
+      v4_store<T>(out + o, acc);
+    }
   }
 }
 
@@ -567,32 +614,79 @@ __global__ __launch_bounds__(256, 3) void dw2_bwdg_kernel(const T* __restrict__ 
   for (int u = 0; u < 2; ++u)
 #pragma unroll
     for (int k = 0; k < 10; ++k) acc[u][k] = pk_splat(0.f);
-#pragma unroll
-  for (int k = 0; k < NIT; ++k) {
-    const int it = pl + k * PPI;
-    const int r = it / TXB, c = it % TXB;
-    const int y = t.ty0 + r, x = t.tx0 + c;
-    if (y >= H || x >= W) continue;
-    cmx_f2 hv[2];
-    v4_unpack<T>(hreg[k], hv);
-    cmx_f2 g[2] = {pk_splat(0.f), pk_splat(0.f)};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
+  if constexpr (PPI == TXB) {
+    // A thread's pixels are rows 0 .. TYB-1 of ONE tile column (c = pl): dz rows r .. r+2 sit
+    // unpacked in registers and slide down one row per pixel (three new taps each, the rows
+    // rotating by renaming in the unrolled loop).  Pixels outside the image contribute nothing:
+    // a column right of the image skips the loop, rows below it are guarded (block-uniform).
+    const int x = t.tx0 + pl;
+    const int nr = H - t.ty0;
+    if (x < W) {
+      const T* dzp = dzc + pl * CB;
+      cmx_f2 win[3][3][2];                          // [dz row % 3][column c .. c+2][pair]
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        cmx_f2 dv[2];
-        v4_unpack<T>(v4_load<T>(dzc + ((r + 2 - i) * EXB + c + 2 - j) * CB), dv);
+        v4_unpack<T>(v4_load<T>(dzp + j * CB), win[0][j]);
+        v4_unpack<T>(v4_load<T>(dzp + (EXB + j) * CB), win[1][j]);
+      }
+      long o = ibase + ((long)t.ty0 * W + x) * C + cq * 4;
+      const long ostep = (long)W * C;
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          g[u] = pk_fma(wr[u][i * 3 + j], dv[u], g[u]);
-          acc[u][i * 3 + j] = pk_fma(hv[u], dv[u], acc[u][i * 3 + j]);
-        }
-        if (i == 1 && j == 1) {
+      for (int k = 0; k < NIT; ++k) {
+        if (k < nr) {
 #pragma unroll
-          for (int u = 0; u < 2; ++u) acc[u][9] += dv[u];
+          for (int j = 0; j < 3; ++j) v4_unpack<T>(v4_load<T>(dzp + ((k + 2) * EXB + j) * CB), win[(k + 2) % 3][j]);
+          cmx_f2 hv[2];
+          v4_unpack<T>(hreg[k], hv);
+          cmx_f2 g[2] = {pk_splat(0.f), pk_splat(0.f)};
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+              const cmx_f2 (&dv)[2] = win[(k + 2 - i) % 3][2 - j];
+#pragma unroll
+              for (int u = 0; u < 2; ++u) {
+                g[u] = pk_fma(wr[u][i * 3 + j], dv[u], g[u]);
+                acc[u][i * 3 + j] = pk_fma(hv[u], dv[u], acc[u][i * 3 + j]);
+              }
+              if (i == 1 && j == 1) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) acc[u][9] += dv[u];
+              }
+            }
+          if (dh) v4_store<T>(dh + o, g);
+          o += ostep;
         }
       }
-    if (dh) v4_store<T>(dh + ibase + ((long)y * W + x) * C + cq * 4, g);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < NIT; ++k) {
+      const int it = pl + k * PPI;
+      const int r = it / TXB, c = it % TXB;
+      const int y = t.ty0 + r, x = t.tx0 + c;
+      if (y >= H || x >= W) continue;
+      cmx_f2 hv[2];
+      v4_unpack<T>(hreg[k], hv);
+      cmx_f2 g[2] = {pk_splat(0.f), pk_splat(0.f)};
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          cmx_f2 dv[2];
+          v4_unpack<T>(v4_load<T>(dzc + ((r + 2 - i) * EXB + c + 2 - j) * CB), dv);
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            g[u] = pk_fma(wr[u][i * 3 + j], dv[u], g[u]);
+            acc[u][i * 3 + j] = pk_fma(hv[u], dv[u], acc[u][i * 3 + j]);
+          }
+          if (i == 1 && j == 1) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) acc[u][9] += dv[u];
+          }
+        }
+      if (dh) v4_store<T>(dh + ibase + ((long)y * W + x) * C + cq * 4, g);
+    }
   }
   // in-wave reduce-scatter over the LPQ lanes of the quad (xor NCQ, 2 NCQ, ...): 40 -> NV
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
