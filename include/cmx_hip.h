@@ -223,6 +223,22 @@ int cmx_upsample_ce_bwd(const void* logits, const int64_t* label, const float* d
  * dlogits (n elements, dtype) = adj * dloss[0] * stats[1]. */
 int cmx_upsample_ce_fwd_adj(const void* logits, const int64_t* label, float* adj, float* out, float* workspace, int B, int h, int w, int H, int W, int K, int ignore_index, int dtype, hipStream_t stream);
 int cmx_upsample_ce_bwd_scale(const float* adj, const float* dloss, const float* stats, void* dlogits, int64_t n, int dtype, hipStream_t stream);
+/* ---- the same one-pass training form for the reference's other criteria (train.py:70-88; H = 4h, W = 4w, K <= 40,
+ *      else CMX_ERR_SHAPE): out = [loss, 1/norm, norm], adj (B, h, w, K) fp32 = bilinear adjoint of the per-pixel
+ *      dl/dz, unscaled; the backward is cmx_upsample_ce_bwd_scale.  workspace: cmx_upsample_loss_workspace bytes.
+ *      kind 0: nn.CrossEntropyLoss(weight=class_weight) (train.py:73 with a weight): loss = sum w_y nll / sum w_y,
+ *              NaN when no pixel is valid; class_weight = K fp32 on the device, or NULL (all ones).
+ *      kind 1: FocalLoss2d (utils/loss_opr.py:12-23): NLLLoss((1 - p)^2 log p) with the same optional weight; the
+ *              exponent is the reference's hard-coded 2.
+ *      kind 2: ce_scale * CrossEntropyLoss + focal_scale * FocalLoss(gamma, alpha) (utils/loss_opr.py:158-202;
+ *              CE_Focal, builder.py:246-247, is (1, 0.2), pure FocalLoss (0, 1)); norm = n_valid; gamma == 0 or
+ *              gamma >= 1 (0, 1, 2, 4 take integer-power paths), class_weight NULL, else CMX_ERR_ARG.  Labels are
+ *              clamped to [0, K) and only label == ignore_index is invalid, as FocalLoss does; with ce_scale == 0
+ *              the quotients use norm + 1e-8 and nothing valid gives loss 0 (FocalLoss), otherwise NaN (torch's
+ *              mean).  With ce_scale != 0 a label outside [0, K) other than ignore_index is unsupported (torch's CE
+ *              asserts on it). */
+size_t cmx_upsample_loss_workspace(int B, int h, int w);
+int cmx_upsample_loss_fwd_adj(const void* logits, const int64_t* label, const float* class_weight, float* adj, float* out, float* workspace, int B, int h, int w, int H, int W, int K, int ignore_index, int kind, float gamma, float alpha, float ce_scale, float focal_scale, int dtype, hipStream_t stream);
 
 /* ---- dense layers: batched MFMA GEMM with fused epilogues -----------------------------
  * Replaces every nn.Linear and 1x1 Conv2d of the path (dual_segformer.py:42-43, 87-96, 110;

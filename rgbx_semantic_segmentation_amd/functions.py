@@ -1628,6 +1628,51 @@ class UpsampleCEF(Function):
         return dl.view(ctx.lshape), None, None, None
 
 
+LOSS_WCE, LOSS_FOCAL2D, LOSS_FOCAL = 0, 1, 2     # cmx_upsample_loss_fwd_adj's `kind`
+
+
+class UpsampleLossF(Function):
+    """F.interpolate(logits, (H, W), bilinear) + one of the criteria beside plain CrossEntropyLoss
+    (train.py:70-88) fused as UpsampleCEF's training form: the forward gives the loss and the unscaled
+    fp32 bilinear adjoint of the per-pixel gradient in one pass (cmx_upsample_loss_fwd_adj), the backward
+    scales it by dloss / normaliser (cmx_upsample_ce_bwd_scale).  spec = (kind, gamma, alpha, ce_scale,
+    focal_scale); weight: K fp32 class weights on the logits' device, or None.  There is no
+    materialised fallback: outside H = 4h, W = 4w, K <= 40 this raises NotImplementedError.  Without a
+    backward to come (validation under no_grad) the same kernel runs and the adjoint is dropped."""
+
+    @staticmethod
+    def forward(ctx, logits, label, dims, ignore, spec, weight):
+        B, h, w, H, W, Kc = dims
+        kind, gamma, alpha, ce_scale, focal_scale = spec
+        logits = _c(logits)
+        if weight is not None and (weight.device != logits.device or weight.dtype != torch.float32
+                                   or weight.numel() != Kc or not weight.is_contiguous()):
+            raise ValueError(f"class weight: {Kc} contiguous fp32 values on {logits.device} expected")
+        out = torch.empty(3, dtype=torch.float32, device=logits.device)
+        adj = torch.empty(B, h * w, Kc, dtype=torch.float32, device=logits.device)
+        ws = K._ws(K.query("cmx_upsample_loss_workspace", B, h, w), logits.device)
+        st = K._lib.try_call("cmx_upsample_loss_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(weight), K.ptr(adj),
+                           K.ptr(out), K.ptr(ws), B, h, w, H, W, Kc, ignore, int(kind), float(gamma), float(alpha),
+                           float(ce_scale), float(focal_scale), K.dtype_code(logits), K.stream())
+        if st == K._lib.CMX_ERR_SHAPE:
+            raise NotImplementedError(f"fused upsample + loss: {K._lib.last_error()}; only CrossEntropyLoss has a "
+                                      "materialised path for other shapes")
+        if st != 0:
+            raise K._lib.CMXError(f"cmx_upsample_loss_fwd_adj failed ({st}): {K._lib.last_error()}")
+        ctx.save_for_backward(adj, out)
+        ctx.ldtype, ctx.lshape = logits.dtype, logits.shape
+        return out[0]             # a view of the kernel's result (no copy launch)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        adj, out = ctx.saved_tensors
+        dloss = _c(dloss.reshape(1).to(torch.float32))
+        dl = torch.empty(ctx.lshape, dtype=ctx.ldtype, device=adj.device)
+        K.call("cmx_upsample_ce_bwd_scale", K.ptr(adj), K.ptr(dloss), K.ptr(out), K.ptr(dl), dl.numel(),
+               K.dtype_code(dl), K.stream())
+        return dl, None, None, None, None, None
+
+
 def upsample_logits_nchw(logits, B, h, w, H, W, Kc):
     out = torch.empty(B, Kc, H, W, dtype=torch.float32, device=logits.device)
     K.call("cmx_bilinear_fwd_nchw_f32", K.ptr(_c(logits)), K.ptr(out), B, h, w, H, W, Kc, K.dtype_code(logits),

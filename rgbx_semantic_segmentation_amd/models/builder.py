@@ -2,7 +2,9 @@
 
 API kept from the reference:
   ``EncoderDecoder(cfg, criterion=nn.CrossEntropyLoss(reduction='mean', ignore_index=255),
-                   norm_layer=nn.BatchNorm2d)``
+                   norm_layer=nn.BatchNorm2d)``; ``criterion`` may also carry a class ``weight``, or be
+  ``utils.loss_opr.FocalLoss`` / ``FocalLoss2d`` or the CE_Focal tuple ``(CrossEntropyLoss, FocalLoss)``
+  (train.py:70-88); anything else raises ``NotImplementedError``
   attributes ``backbone``, ``decode_head``, ``criterion``, ``channels``, ``aux_head = None``;
   ``forward(rgb, modal_x, label=None)`` -> 0-dim loss (with autograd graph) if ``label`` is
   given, else fp32 logits (B, K, H, W); ``encode_decode``; ``init_weights``; ``state_dict``
@@ -66,6 +68,59 @@ def backward_segment(name: str) -> int:
     return 0
 
 
+SUPPORTED_CRITERIA = ("nn.CrossEntropyLoss(reduction='mean'[, weight=w]), FocalLoss(reduction='mean', gamma == 0 or "
+                      "gamma >= 1), FocalLoss2d(reduction='mean'[, weight=w]) and CE_Focal = the tuple "
+                      "(nn.CrossEntropyLoss(reduction='mean'), FocalLoss(...))")
+
+
+def _loss_plan(criterion):
+    """(ignore_index, spec, class weight) of a supported criterion (train.py:70-88), else
+    NotImplementedError naming the supported set.  spec None: plain CrossEntropyLoss, the
+    UpsampleCEF path; otherwise UpsampleLossF's (kind, gamma, alpha, ce_scale, focal_scale)."""
+    from ..utils.loss_opr import CE_FOCAL_WEIGHT, FocalLoss, FocalLoss2d, check_focal_gamma
+
+    def refuse(why):
+        raise NotImplementedError(f"criterion: {why}; on the hot path: {SUPPORTED_CRITERIA}")
+
+    def plain_ce(c):
+        if not isinstance(c, nn.CrossEntropyLoss):
+            return False
+        if c.reduction != "mean":
+            refuse(f"CrossEntropyLoss(reduction={c.reduction!r})")
+        if c.label_smoothing != 0.0:
+            refuse("CrossEntropyLoss with label_smoothing")
+        return True
+
+    def focal(c):
+        if c.reduction != "mean":
+            refuse(f"FocalLoss(reduction={c.reduction!r})")
+        return check_focal_gamma(c.gamma), float(c.alpha)     # ValueError on 0 < gamma < 1
+
+    if plain_ce(criterion):
+        if criterion.weight is None:
+            return int(criterion.ignore_index), None, None
+        return int(criterion.ignore_index), (F.LOSS_WCE, 0.0, 0.0, 1.0, 0.0), criterion.weight
+    if isinstance(criterion, FocalLoss):
+        gamma, alpha = focal(criterion)
+        return int(criterion.ignore_label), (F.LOSS_FOCAL, gamma, alpha, 0.0, 1.0), None
+    if isinstance(criterion, FocalLoss2d):
+        if criterion.loss.reduction != "mean":
+            refuse(f"FocalLoss2d(reduction={criterion.loss.reduction!r})")
+        return int(criterion.loss.ignore_index), (F.LOSS_FOCAL2D, 0.0, 0.0, 1.0, 0.0), criterion.loss.weight
+    if isinstance(criterion, (tuple, list)) and len(criterion) == 2 and isinstance(criterion[1], FocalLoss) \
+            and plain_ce(criterion[0]):
+        ce, fl = criterion
+        if ce.weight is not None:
+            refuse("CE_Focal with a class weight")
+        if int(ce.ignore_index) != int(fl.ignore_label):
+            refuse("CE_Focal whose two terms ignore different labels")
+        gamma, alpha = focal(fl)
+        # CE + 0.2 * Focal (builder.py:246-247).  Labels outside [0, K) other than the ignore value are
+        # unsupported here: torch's CrossEntropyLoss asserts on them (the kernel clamps them, as FocalLoss)
+        return int(ce.ignore_index), (F.LOSS_FOCAL, gamma, alpha, 1.0, CE_FOCAL_WEIGHT), None
+    refuse(type(criterion).__name__)
+
+
 class EncoderDecoder(nn.Module):
     # the forward is one stream-ordered sequence of library launches with no host sync: callers
     # may capture it in a HIP graph (the evaluator does, per crop-batch shape)
@@ -86,13 +141,10 @@ class EncoderDecoder(nn.Module):
         ffm = _get(cfg, "feature_fusion_module", "FFM")
         if criterion is None:
             criterion = nn.CrossEntropyLoss(reduction="mean", ignore_index=int(_get(cfg, "background", 255)))
-        if not isinstance(criterion, nn.CrossEntropyLoss) or criterion.reduction != "mean" or \
-                criterion.weight is not None or criterion.label_smoothing != 0.0:
-            raise NotImplementedError("criterion: only CrossEntropyLoss(reduction='mean') is on the hot path")
         self.cfg = cfg
         self.norm_layer = norm_layer
-        self.criterion = criterion
-        self.ignore_index = int(criterion.ignore_index)
+        self.criterion = criterion         # the object(s) as given, as the reference keeps them
+        self.ignore_index, self._loss_spec, self._loss_weight = _loss_plan(criterion)
         self.backbone_name = backbone
         self.channels = list(MIT_SPECS[backbone]["embed_dims"])
         self.backbone = BACKBONES[backbone](norm_fuse=norm_layer, frm=frm, ffm=ffm)
@@ -149,6 +201,11 @@ class EncoderDecoder(nn.Module):
                                     conv_pad={"backbone.patch_embed1.proj.weight": PE1_KPAD,
                                               "backbone.extra_patch_embed1.proj.weight": PE1_KPAD},
                                     segment_of=backward_segment)
+        if self._loss_weight is not None:      # the class weights: moved once, outside any capture
+            self._loss_weight = self._loss_weight.detach().to(device=device, dtype=torch.float32).contiguous()
+            if self._loss_weight.numel() != self.num_classes:
+                raise ValueError(f"criterion weight has {self._loss_weight.numel()} entries, num_classes is "
+                                 f"{self.num_classes}")
         from .. import deferred
         deferred.reserve()          # pinned launch-record tables for captured backward passes
         # every BatchNorm's num_batches_tracked is a view into one counter: one increment per
@@ -253,4 +310,7 @@ class EncoderDecoder(nn.Module):
         logits, (h, w) = self._logits_lowres(rgb, modal_x)
         B, _, H, W = rgb.shape
         label = label.to(device=logits.device, dtype=torch.int64).contiguous()
-        return F.UpsampleCEF.apply(logits, label, (B, h, w, H, W, self.num_classes), self.ignore_index)
+        dims = (B, h, w, H, W, self.num_classes)
+        if self._loss_spec is None:        # plain CrossEntropyLoss
+            return F.UpsampleCEF.apply(logits, label, dims, self.ignore_index)
+        return F.UpsampleLossF.apply(logits, label, dims, self.ignore_index, self._loss_spec, self._loss_weight)

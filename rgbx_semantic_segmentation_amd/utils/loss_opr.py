@@ -1,0 +1,114 @@
+"""The criteria beside ``nn.CrossEntropyLoss`` that the fused upsample + loss kernels cover
+(reference: utils/loss_opr.py; selected by train.py:70-88), with the reference's constructor
+signatures at the reference's import path.
+
+On the training hot path ``EncoderDecoder`` never calls these modules' ``forward``: it reads
+their hyper-parameters and runs ``cmx_upsample_loss_fwd_adj`` on the low-resolution logits
+(functions.UpsampleLossF).  ``forward(pred, target)`` is the plain-PyTorch statement of the same
+math on full-resolution logits (B, K, H, W): API compatibility off the hot path, and the tests'
+fp64 reference.  ``focal_grad`` / ``focal2d_grad`` are the closed-form per-pixel gradients the
+kernels implement.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+FOCAL_EPS = 1e-8
+CE_FOCAL_WEIGHT = 0.2       # CE_Focal: loss = CE + 0.2 * Focal (reference builder.py:246-247)
+
+
+def check_focal_gamma(gamma) -> float:
+    """The kernels take gamma == 0 or gamma >= 1 (x^(gamma-1) of the gradient is unbounded at
+    x = 0 in between)."""
+    g = float(gamma)
+    if not (g == 0.0 or g >= 1.0):
+        raise ValueError(f"FocalLoss gamma={gamma!r}: only gamma == 0 or gamma >= 1 is supported")
+    return g
+
+
+class FocalLoss(nn.Module):
+    """Sum over ALL K classes per pixel of -a_k (1 - pt_k)^gamma log(pt_k + 1e-8), with
+    pt_k = p_k, a_k = alpha at the target class and pt_k = 1 - p_k, a_k = 1 - alpha elsewhere;
+    mean = sum over valid pixels / (n_valid + 1e-8), so nothing valid gives 0, not NaN.
+    valid = (target != ignore_label); the class is clamp(target, 0, K - 1): an out-of-range
+    label that is not the ignore value is clamped, not ignored."""
+
+    def __init__(self, ignore_label, gamma=2.0, alpha=0.25, reduction='mean'):
+        super().__init__()
+        self.ignore_label = ignore_label
+        self.gamma = gamma
+        self.alpha = alpha
+        self.reduction = reduction
+
+    def pixel_loss(self, pred, target):
+        """(loss (B, H, W) summed over classes and zeroed at invalid pixels, valid mask)."""
+        K = pred.shape[1]
+        valid = target != self.ignore_label
+        onehot = F.one_hot(target.clamp(0, K - 1), K).movedim(-1, 1).bool()
+        p = torch.softmax(pred, dim=1)
+        pt = torch.where(onehot, p, 1 - p)
+        a = torch.where(onehot, torch.full_like(p, self.alpha), torch.full_like(p, 1 - self.alpha))
+        loss = -a * (1 - pt) ** self.gamma * torch.log(pt + FOCAL_EPS)
+        return loss.sum(1) * valid.to(loss.dtype), valid
+
+    def forward(self, pred, target):
+        loss, valid = self.pixel_loss(pred, target)
+        if self.reduction == 'mean':
+            return loss.sum() / (valid.to(loss.dtype).sum() + FOCAL_EPS)
+        if self.reduction == 'sum':
+            return loss.sum()
+        return loss.flatten(1)
+
+
+class FocalLoss2d(nn.Module):
+    """NLLLoss of (1 - p)^2 log p.  The exponent is the reference's hard-coded 2: the
+    constructor's ``gamma`` is stored and otherwise IGNORED, as in the reference.  ``weight``: a
+    sequence of K class weights (NLLLoss's weighted mean), or None."""
+
+    def __init__(self, gamma=0, weight=None, reduction='mean', ignore_index=255):
+        super().__init__()
+        self.gamma = gamma
+        w = None if weight is None else torch.as_tensor(weight, dtype=torch.float32).flatten().clone()
+        self.loss = nn.NLLLoss(weight=w, reduction=reduction, ignore_index=ignore_index)
+
+    def forward(self, input, target):
+        return self.loss((1 - F.softmax(input, 1)) ** 2 * F.log_softmax(input, 1), target)
+
+
+# ------------------------------------------------------------------ closed-form gradients
+def focal_grad(z, target, ignore_label, gamma, alpha):
+    """d(per-pixel FocalLoss)/dz for logits z (B, K, H, W), zero at invalid pixels (no 1/n):
+    u_k = dl/dp_k, dl/dz_j = p_j (u_j - sum_k u_k p_k)."""
+    K = z.shape[1]
+    valid = (target != ignore_label).unsqueeze(1)
+    onehot = F.one_hot(target.clamp(0, K - 1), K).movedim(-1, 1).bool()
+    p = torch.softmax(z, dim=1)
+    q = 1 - p
+    x = torch.where(onehot, q, p)                     # 1 - pt
+    y = torch.where(onehot, p, q) + FOCAL_EPS         # pt + eps
+    a = torch.where(onehot, torch.full_like(p, alpha), torch.full_like(p, alpha - 1))
+    u = -x ** gamma / y
+    if gamma != 0:
+        u = u + gamma * x ** (gamma - 1) * torch.log(y)
+    u = a * u
+    g = p * (u - (u * p).sum(1, keepdim=True))
+    return g * valid.to(g.dtype)
+
+
+def focal2d_grad(z, target, ignore_index, weight=None):
+    """d(per-pixel w_y * -(1 - p_y)^2 log p_y)/dz = c (p - onehot),
+    c = w_y ((1 - p_y)^2 - 2 p_y (1 - p_y) log p_y); zero at ignored pixels."""
+    K = z.shape[1]
+    valid = target != ignore_index
+    t = torch.where(valid, target, torch.zeros_like(target))
+    onehot = F.one_hot(t, K).movedim(-1, 1).to(z.dtype)
+    lp = torch.log_softmax(z, dim=1)
+    p = lp.exp()
+    lpy = (lp * onehot).sum(1, keepdim=True)
+    py = lpy.exp()
+    c = (1 - py) ** 2 - 2 * py * (1 - py) * lpy
+    if weight is not None:
+        c = c * weight.to(z.dtype)[t].unsqueeze(1)
+    return c * (p - onehot) * valid.unsqueeze(1).to(z.dtype)

@@ -46,6 +46,45 @@ def ce():
             "ce_bwd_scale (training)": timeit(scale)}
 
 
+def loss():
+    """The loss family's forward-adjoint (cmx_upsample_loss_fwd_adj; one launch + the finalize) at the
+    B2 shape (2, 120, 160, 40) bf16, per criterion, beside the CE training form and beside the same
+    loss in eager PyTorch on the GPU (F.interpolate + the utils/loss_opr.py restatement, forward +
+    backward): the eager column is what a speed-up is quoted against."""
+    import torch.nn.functional as Fn
+    sys.path.insert(0, "tests")
+    import loss_cases as lc
+    from rgbx_semantic_segmentation_amd.models.builder import _loss_plan
+    B, h, w, Kc = 2, 120, 160, 40
+    H, W = 4 * h, 4 * w
+    logits = torch.randn(B, h * w, Kc, device="cuda").to(torch.bfloat16)
+    label = torch.randint(0, Kc, (B, H, W), device="cuda")
+    label[:, :20, :20] = 255
+    out = torch.empty(3, device="cuda")
+    adj = torch.empty(B, h * w, Kc, device="cuda")
+    ws = K._ws(K.query("cmx_upsample_loss_workspace", B, h, w), "cuda")
+    wsc = K._ws(K.query("cmx_upsample_ce_workspace", B, H, W), "cuda")
+    res = {"ce_fwd_adj (plain CE)": timeit(lambda: K.call(
+        "cmx_upsample_ce_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(adj), K.ptr(out), K.ptr(wsc), B, h, w, H, W, Kc,
+        255, 1, K.stream()))}
+    for name in lc.CRITERIA:
+        crit = lc.make_criterion(name, Kc)
+        ignore, spec, weight = _loss_plan(crit)
+        weight = None if weight is None else weight.cuda().float().contiguous()
+        res[f"loss_fwd_adj {name}"] = timeit(lambda: K.call(
+            "cmx_upsample_loss_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(weight), K.ptr(adj), K.ptr(out), K.ptr(ws),
+            B, h, w, H, W, Kc, ignore, *spec, 1, K.stream()))
+        eager = lc.Restated(crit).cuda()
+        x = logits.view(B, h, w, Kc).permute(0, 3, 1, 2).float().requires_grad_(True)
+
+        def step():
+            x.grad = None
+            up = Fn.interpolate(x, size=(H, W), mode="bilinear", align_corners=False)
+            eager(up, label).backward()
+        res[f"eager fwd+bwd {name}"] = timeit(step, iters=10)
+    return res
+
+
 def decoder():
     """The decoder fold's full-resolution passes at the B2 shapes: the upsample-sum (up3) + the c1
     residual GEMM against the c1 GEMM with the upsample in its epilogue, and the 3-grid adjoint

@@ -33,6 +33,8 @@ from rgbx_semantic_segmentation_amd.utils.pyt_utils import all_reduce_tensor  # 
 
 logger = get_logger()
 
+CRITERIA = ("CrossEntropyLoss", "FocalLoss", "FocalLoss2d", "CE_Focal")
+
 
 def build_parser():
     p = argparse.ArgumentParser()
@@ -49,7 +51,12 @@ def build_parser():
     p.add_argument("--warm-up-epoch", type=int, default=10)
     p.add_argument("--compute-dtype", default=None, choices=["bfloat16", "float32", "float16"],
                    help="default: float16 with --use-mixed-precision (the reference's fp16 autocast), else bfloat16")
-    p.add_argument("--criterion", default="CrossEntropyLoss")
+    p.add_argument("--criterion", default="CrossEntropyLoss",
+                   help="config.criterion (train.py:70-88): " + ", ".join(CRITERIA))
+    p.add_argument("--fl-gamma", type=float, default=4.0, help="config.FL_gamma (config.py:64)")
+    p.add_argument("--fl-alpha", type=float, default=0.25, help="config.FL_alpha (config.py:65)")
+    p.add_argument("--class-weights", default="",
+                   help="comma-separated class weights (num-classes floats) for CrossEntropyLoss / FocalLoss2d")
     p.add_argument("--optimizer", default="AdamW")
     p.add_argument("--seed", type=int, default=12345)
     p.add_argument("--use-mixed-precision", action="store_true",
@@ -69,6 +76,29 @@ def build_parser():
     return p
 
 
+def build_criterion(args, background=255):
+    """The criterion object(s) train.py:70-88 builds for config.criterion; other names raise."""
+    from torch import nn
+    from rgbx_semantic_segmentation_amd.utils.loss_opr import FocalLoss, FocalLoss2d
+    if args.criterion not in CRITERIA:
+        raise NotImplementedError(f"criterion {args.criterion} (on the HIP path: {', '.join(CRITERIA)})")
+    weight = None
+    if args.class_weights:
+        weight = [float(v) for v in args.class_weights.split(",")]
+        if len(weight) != args.num_classes:
+            raise ValueError(f"--class-weights has {len(weight)} values, --num-classes is {args.num_classes}")
+        if args.criterion in ("FocalLoss", "CE_Focal"):
+            raise NotImplementedError(f"--class-weights with {args.criterion}: FocalLoss takes no class weight")
+    focal = lambda: FocalLoss(ignore_label=background, gamma=args.fl_gamma, alpha=args.fl_alpha, reduction="mean")
+    if args.criterion == "FocalLoss":
+        return focal()
+    if args.criterion == "FocalLoss2d":
+        return FocalLoss2d(weight=weight, ignore_index=background, reduction="mean")
+    ce = nn.CrossEntropyLoss(weight=None if weight is None else torch.tensor(weight), reduction="mean",
+                             ignore_index=background)
+    return (ce, focal()) if args.criterion == "CE_Focal" else ce
+
+
 def resolve_precision(args):
     """(compute dtype, dynamic loss scaling on?).  The reference runs fp16 only under autocast
     with a GradScaler (train.py:185-198), so fp16 storage always turns loss scaling on, as in
@@ -83,8 +113,7 @@ def main(argv=None):
         args = engine.args
         seed = engine.local_rank if engine.distributed else args.seed
         torch.manual_seed(seed)
-        if args.criterion != "CrossEntropyLoss":
-            raise NotImplementedError(f"criterion {args.criterion} (only CrossEntropyLoss is on the HIP path)")
+        criterion = build_criterion(args)
         if args.optimizer != "AdamW":
             raise NotImplementedError(f"optimizer {args.optimizer} (only AdamW is on the HIP path)")
         if not torch.cuda.is_available():
@@ -119,7 +148,7 @@ def main(argv=None):
         dtype, loss_scaling = resolve_precision(args)
         cfg = dict(backbone=args.backbone, num_classes=args.num_classes, compute_dtype=dtype,
                    decoder_embed_dim=512)
-        model = EncoderDecoder(cfg, norm_layer=norm).to(dev)
+        model = EncoderDecoder(cfg, criterion=criterion, norm_layer=norm).to(dev)
         sync = None
         if engine.distributed:
             group = torch.distributed.group.WORLD
