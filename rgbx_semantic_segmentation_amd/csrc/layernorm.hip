@@ -8,6 +8,7 @@
 // Layout: a row is C contiguous elements; TPR lanes own one row, each lane NCH chunks
 // of one 16-byte vector.  HBM-bound: fwd reads x once and writes y once (+8 B/row stats).
 #include "cmx_common.h"
+#include "ln_plan.h"
 
 // RPT rows per thread, spaced RPB apart: every row's loads are issued before any reduction, so
 // a narrow-row launch (C = 64 / 128: one 16-B chunk per lane) keeps RPT loads in flight per lane
@@ -261,22 +262,13 @@ int cmx_reduce_partials_strided(const float* ws, float* out, int nblk, int W, in
   return cmx_check_launch("reduce_partials_strided");
 }
 
-static int ln_tpr(int chunks) {
-  int t = 1;
-  while (t < chunks && t < 64) t <<= 1;
-  return t < 4 ? 4 : t;
-}
-
+// the launch policy (<TPR, NCH, RPT>, grid, backward blocks and workspace) is ln_plan.h
 template <typename T>
 static int ln_fwd_launch(const void* x, const float* g, const float* b, void* y, float* mu, float* rs,
                          long R, int G, int C, float eps, hipStream_t s) {
-  constexpr int V = VecT<T>::N;
-  const int chunks = C / V;
-  const int tpr = ln_tpr(chunks);
-  const int nch = (chunks + tpr - 1) / tpr;
-  // 4 rows per thread for narrow rows when that still leaves >= 256 blocks (one per CU)
-  const int rpt = (nch == 1 && tpr <= 16 && R * G / ((256 / tpr) * 4) >= 256) ? 4 : 1;
-  const dim3 grid(cdiv(R, (256 / tpr) * rpt), G);
+  const lnplan::LnPlan p = lnplan::plan_ln_fwd(R, G, C, VecT<T>::N);
+  const int tpr = p.tpr, nch = p.nch, rpt = p.rpt;
+  const dim3 grid(p.grid_x, p.grid_y);
 #define LNF(TPR, NCH, RPT)                                                                  \
   if (tpr == TPR && nch == NCH && rpt == RPT) {                                             \
     hipLaunchKernelGGL((ln_fwd_kernel<T, TPR, NCH, RPT>), grid, dim3(256), 0, s, (const T*)x, g, b, \
@@ -290,24 +282,14 @@ static int ln_fwd_launch(const void* x, const float* g, const float* b, void* y,
   return CMX_ERR_SHAPE;
 }
 
-static int ln_bwd_blocks(long R, int rpb) {     // <= 512 blocks per group: ~2 rows per thread at stage 1
-  long nb = (R + rpb - 1) / rpb;
-  return (int)(nb < 512 ? nb : 512);
-}
-
 template <typename T>
 static int ln_bwd_launch(const void* dy, const void* x, const float* g, const float* mu,
                          const float* rs, void* dx, float* dgamma, float* dbeta, float* ws, long R,
                          int G, int C, int accumulate, const void* dres, const float* sscale, void* dxs,
                          long rps, const void* dy2, hipStream_t s) {
-  constexpr int V = VecT<T>::N;
-  const int chunks = C / V;
-  const int tpr = ln_tpr(chunks);
-  const int nch = (chunks + tpr - 1) / tpr;
-  const int nb = ln_bwd_blocks(R, 256 / tpr);
-  const dim3 grid(nb, G);
-  // two rows per iteration where a thread walks more than one (narrow rows, stage 1 / 2)
-  const int rpt = (nch == 1 && tpr <= 16 && R > (long)nb * (256 / tpr)) ? 2 : 1;
+  const lnplan::LnPlan p = lnplan::plan_ln_bwd(R, G, C, VecT<T>::N);
+  const int tpr = p.tpr, nch = p.nch, rpt = p.rpt, nb = p.nb;
+  const dim3 grid(p.grid_x, p.grid_y);
 #define LNB(TPR, NCH, RPT)                                                                  \
   if (tpr == TPR && nch == NCH && rpt == RPT) {                                             \
     hipLaunchKernelGGL((ln_bwd_kernel<T, TPR, NCH, RPT>), grid, dim3(256), 0, s, (const T*)dy, \
@@ -350,9 +332,7 @@ int cmx_layernorm_fwd(const void* x, const float* gamma, const float* beta, void
 }
 
 size_t cmx_layernorm_bwd_workspace(long R, int G, int C, int dtype) {
-  const int V = dtype == 0 ? 4 : 8;
-  const int tpr = ln_tpr(C / V);
-  return (size_t)G * ln_bwd_blocks(R, 256 / tpr) * 2 * C * sizeof(float);
+  return lnplan::plan_ln_bwd(R, G, C, lnplan::vec_width(dtype)).ws_bytes;
 }
 
 // dx (dtype), dgamma/dbeta (G, C) fp32 (overwritten, or accumulated if accumulate=1).

@@ -307,17 +307,13 @@ class LayerNormResF(Function):
         dy = _c(dy) if dy is not None else torch.zeros_like(x)
         dy2 = _c(dy2) if dy2 is not None else None
         dres = _c(dres) if dres is not None else None
-        dx = torch.empty_like(x)
         dxs = torch.empty_like(x) if (tap is not None and scale is not None) else None
-        nbytes = K.query("cmx_layernorm_bwd_workspace", R, G, C, K.dtype_code(x))
-        ws = K._ws(nbytes, x.device)
         defer = deferred.ENABLED
-        K.call("cmx_layernorm_bwd_res", K.ptr(dy), K.ptr(dy2), K.ptr(x), K.ptr(gamma), K.ptr(mean), K.ptr(rstd), K.ptr(dres),
-               K.ptr(scale), K.ptr(dxs), K.ptr(dx), 0 if defer else K.ptr(gg), 0 if defer else K.ptr(bg),
-               K.ptr(ws), R, G, C, int(rps), 0, K.dtype_code(x), K.stream())
+        dx, part = K.layernorm_bwd_res(dy, x, gamma, mean, rstd, G, None if defer else gg, None if defer else bg,
+                                       dy2=dy2, dres=dres, sscale=scale, rows_per_sample=rps, dxs=dxs)
         if defer:
-            nb = nbytes // (8 * G * C)
-            deferred.reduce(ws, gg, bg, G, nb, nb * 2 * C, 2 * C, 1, 2 * C, C, gg.stride(0), 0, bg.stride(0), 0)
+            nb = part.shape[1]
+            deferred.reduce(part, gg, bg, G, nb, nb * 2 * C, 2 * C, 1, 2 * C, C, gg.stride(0), 0, bg.stride(0), 0)
         if dxs is not None:
             tap.put(dxs)
         return dx, None, None, None, None, None, None, None, None, None, None, None, None

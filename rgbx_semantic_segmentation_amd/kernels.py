@@ -58,6 +58,25 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, G: int, dgamma: torch.Tensor, dbeta:
     return dx
 
 
+def layernorm_bwd_res(dy, x, gamma, mean, rstd, G: int, dgamma=None, dbeta=None, dy2=None, dres=None, sscale=None,
+                      rows_per_sample: int = 1, dxs=None, accumulate: bool = False):
+    """cmx_layernorm_bwd_res: upstream dy + dy2, dx = dres + LN_bwd, dxs = sscale[row // rows_per_sample] * dx
+    (dy2 / dres / sscale / dxs optional; dxs is the caller's).  Returns (dx, partials): with dgamma = dbeta =
+    None nothing is reduced and partials, the workspace seen as (G, nb, 2C) = [dgamma | dbeta] per block,
+    is what the caller reduces (the deferred mode)."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    R = rows // G
+    dx = torch.empty_like(x)
+    nbytes = query("cmx_layernorm_bwd_workspace", R, G, C, dtype_code(x))
+    ws = _ws(nbytes, x.device)
+    call("cmx_layernorm_bwd_res", ptr(dy), ptr(dy2), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres),
+         ptr(sscale), ptr(dxs), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), R, G, C, int(rows_per_sample),
+         int(accumulate), dtype_code(x), stream())
+    nb = nbytes // (8 * G * C)
+    return dx, ws[:G * nb * 2 * C].view(G, nb, 2 * C)
+
+
 # ------------------------------------------------------------------------------ elementwise
 def residual_add(x, y, sample_scale=None, out=None, n_per_sample=None):
     out = torch.empty_like(x) if out is None else out
