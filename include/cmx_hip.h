@@ -353,6 +353,17 @@ int cmx_adamw_step_segment(float* p, const float* g, float* m, float* v, void* s
  *      optimizer's parameters. */
 int cmx_grad_nonfinite(const float* g, int64_t n, const uint8_t* flags64, float* found_inf, hipStream_t stream);
 int cmx_loss_scale_update(float* scale, int* growth_tracker, float* found_inf, float growth_factor, float backoff_factor, int growth_interval, hipStream_t stream);
+/* ---- fused SGD with momentum over the flat parameter buffer: torch.optim.SGD(params_list, lr, momentum,
+ *      weight_decay) of config.optimizer == 'SGDM' (train.py:116-117,130-131) on group_weight's two groups
+ *      (init_func.py:33-57), single-tensor order with dampening 0:
+ *        g1 = g * grad_scale / loss_scale[0]; g1 += wd * p (flag 1); buf = mu * buf + g1;
+ *        d = nesterov ? g1 + mu * buf : buf; p -= lr_ptr[0] * d; shadow = 16-bit copy of p.
+ *      buf is NULL exactly when momentum == 0 (that instance never touches it); decay64 is adamw_step's
+ *      per-64-element flag (2 = frozen, untouched); loss_scale and found_inf are nullable, and found_inf[0] != 0
+ *      skips the whole step as adamw_step_scaled does; n is a multiple of 64; max_blocks > 0 caps the grid.
+ *      Refusals (CMX_ERR_SHAPE for n, CMX_ERR_ARG otherwise) precede the launch; nothing is allocated or
+ *      synchronised, so the call is capturable. */
+int cmx_sgdm_step(float* p, const float* g, float* buf, void* shadow, int shadow_dtype, const uint8_t* decay64, int64_t n, const float* lr_ptr, double momentum, double weight_decay, int nesterov, float grad_scale, const float* loss_scale, const float* found_inf, int max_blocks, hipStream_t stream);
 
 /* ---- IFRM (ImprovedFeatureRectifyModule, net_utils.py:155-180; config.py:57 'IFRM').
  *      mul2: out = a * b (fp32; the channel gate y * sigmoid(gate(y)), :61-63), bwd da = d*b, db = d*a.

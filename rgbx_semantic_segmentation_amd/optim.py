@@ -13,6 +13,9 @@ Host-visible state the reference loop touches is kept compatible:
     ``step``/``exp_avg``/``exp_avg_sq``) so checkpoints written by either side load.
 With a process group of world size > 1, ``step()`` first averages gradients (RCCL
 all-reduce of the flat buffer, see dist.py) unless the caller already did.
+
+``FusedSGD`` is the same construction for the reference's ``config.optimizer == 'SGDM'``
+(``torch.optim.SGD`` with momentum, csrc/sgdm.hip).
 """
 from __future__ import annotations
 
@@ -127,6 +130,103 @@ class FusedAdamW:
             s._param_view(self.exp_avg, sl).copy_(st["exp_avg"])
             s._param_view(self.exp_avg_sq, sl).copy_(st["exp_avg_sq"])
             self.step_t.fill_(float(st["step"]))
+        for g, gs in zip(self.param_groups, sd["param_groups"]):
+            g["lr"] = gs["lr"]
+
+
+class FusedSGD:
+    """``torch.optim.SGD(group_weight(model), lr, momentum, weight_decay=...)`` (the reference's
+    ``config.optimizer == 'SGDM'``, train.py:116-117,130-131) in ONE launch over the flat buffers
+    (csrc/sgdm.hip), which also refreshes the 16-bit weight shadow.  The same two groups, LR device
+    scalar, ``grad_sync`` fold and ``GradScaler`` skip as ``FusedAdamW``; ``state_dict()`` /
+    ``load_state_dict()`` use torch.optim.SGD's format (per-parameter ``momentum_buffer``; zeros
+    before the first step, which with dampening 0 steps exactly as torch's absent buffer does).
+    With momentum 0 there is no buffer and the kernel instance never touches one."""
+
+    def __init__(self, model, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
+                 grad_sync=None):
+        # torch.optim.SGD's own refusals, then what the kernel does not implement
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if dampening != 0:
+            raise NotImplementedError(f"dampening {dampening}: the fused SGD kernel implements dampening 0 only "
+                                      "(the reference never sets it)")
+        if maximize:
+            raise NotImplementedError("maximize=True: the fused SGD kernel only descends (the reference never sets it)")
+        store = model.store
+        if store is None:
+            raise RuntimeError("model.cuda() must be called before building the optimizer")
+        self.store = store
+        self.momentum, self.weight_decay, self.nesterov = float(momentum), float(weight_decay), bool(nesterov)
+        dev = store.device
+        self.momentum_buffer = torch.zeros_like(store.flat) if self.momentum != 0 else None
+        self.lr_t = torch.full((1,), float(lr), dtype=torch.float32, device=dev)
+        self._lr_written = float(lr)
+        self.grad_sync = grad_sync          # callable(flat_grad) -> grad scale, or None
+        names = list(store.params.keys())
+        decay = [store.params[n] for n in names if store.slots[n].decay]
+        no_decay = [store.params[n] for n in names if not store.slots[n].decay and not store.slots[n].frozen]
+        self._order = decay + no_decay      # index order used by state_dict (group_weight order)
+        common = dict(momentum=self.momentum, dampening=0, nesterov=self.nesterov, maximize=False, foreach=None,
+                      differentiable=False, fused=None)
+        self.param_groups = [
+            _Group(self, params=decay, lr=float(lr), weight_decay=self.weight_decay, **common),
+            _Group(self, params=no_decay, lr=float(lr), weight_decay=0.0, **common),
+        ]
+        self.defaults = dict(lr=float(lr), weight_decay=self.weight_decay, **common)
+
+    _set_lr = FusedAdamW._set_lr
+    zero_grad = FusedAdamW.zero_grad
+
+    @torch.no_grad()
+    def step(self, closure=None, scaler: "GradScaler | None" = None):
+        s = self.store
+        gscale = 1.0
+        if self.grad_sync is not None:
+            gscale = float(self.grad_sync(s.grad))
+        loss_scale = found_inf = None
+        if scaler is not None and scaler.enabled:
+            # GradScaler.step, as in FusedAdamW.step: flag inf / nan, then unscale or skip in the kernel
+            call("cmx_grad_nonfinite", ptr(s.grad), s.numel, ptr(s.decay64), ptr(scaler.found_inf), stream())
+            loss_scale, found_inf = scaler.scale_t, scaler.found_inf
+        call("cmx_sgdm_step", ptr(s.flat), ptr(s.grad), ptr(self.momentum_buffer), ptr(s.shadow), s.shadow_code,
+             ptr(s.decay64), s.numel, ptr(self.lr_t), self.momentum, self.weight_decay, int(self.nesterov), gscale,
+             ptr(loss_scale), ptr(found_inf), 0, stream())
+        return None
+
+    # ------------------------------------------------------------------ checkpoint format
+    def state_dict(self):
+        s = self.store
+        state = {}
+        for i, p in enumerate(self._order):
+            state[i] = {} if self.momentum_buffer is None else \
+                {"momentum_buffer": s._param_view(self.momentum_buffer, s.slot(p)).detach().clone()}
+        groups, idx = [], 0
+        for g in self.param_groups:
+            d = {k: v for k, v in g.items() if k != "params"}
+            d["params"] = list(range(idx, idx + len(g["params"])))
+            idx += len(g["params"])
+            groups.append(d)
+        return {"state": state, "param_groups": groups}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        s = self.store
+        if self.momentum_buffer is not None:
+            for i, p in enumerate(self._order):
+                st = sd["state"].get(i, sd["state"].get(str(i)))
+                buf = None if st is None else st.get("momentum_buffer")
+                view = s._param_view(self.momentum_buffer, s.slot(p))
+                if buf is None:             # torch before its first step: the same update as zeros
+                    view.zero_()
+                else:
+                    view.copy_(buf)
         for g, gs in zip(self.param_groups, sd["param_groups"]):
             g["lr"] = gs["lr"]
 

@@ -6,8 +6,8 @@
 Same sequence per iteration as the reference: H2D copy, ``loss = model(rgb, modal_x, gt)``,
 (distributed) loss all-reduce for logging, ``optimizer.zero_grad()`` (a no-op: backward
 overwrites the flat gradient buffer), ``loss.backward()``, ``optimizer.step()`` (RCCL
-gradient all-reduce + fused AdamW), THEN the WarmUpPolyLR update (the LR lands one step
-late, as in the reference).  Differences: DistributedDataParallel is replaced by the flat
+gradient all-reduce + fused AdamW, or fused SGD with momentum under --optimizer SGDM), THEN
+the WarmUpPolyLR update (the LR lands one step late, as in the reference).  Differences: DistributedDataParallel is replaced by the flat
 gradient all-reduce (dist.py); data is the synthetic dataset unless --dataset-path names one
 in the reference's layout (then RGBXDataset + TrainPre on the GPU, augment.py);
 TensorBoard logging is omitted (tensorboardX is not installed).
@@ -34,6 +34,7 @@ from rgbx_semantic_segmentation_amd.utils.pyt_utils import all_reduce_tensor  # 
 logger = get_logger()
 
 CRITERIA = ("CrossEntropyLoss", "FocalLoss", "FocalLoss2d", "CE_Focal")
+OPTIMIZERS = ("AdamW", "SGDM")
 
 
 def build_parser():
@@ -57,7 +58,9 @@ def build_parser():
     p.add_argument("--fl-alpha", type=float, default=0.25, help="config.FL_alpha (config.py:65)")
     p.add_argument("--class-weights", default="",
                    help="comma-separated class weights (num-classes floats) for CrossEntropyLoss / FocalLoss2d")
-    p.add_argument("--optimizer", default="AdamW")
+    p.add_argument("--optimizer", default="AdamW",
+                   help="config.optimizer (train.py:114-135): " + ", ".join(OPTIMIZERS))
+    p.add_argument("--momentum", type=float, default=0.9, help="config.momentum (config.py:70), SGDM only")
     p.add_argument("--seed", type=int, default=12345)
     p.add_argument("--use-mixed-precision", action="store_true",
                    help="config.use_mixed_precision (config.py:61): dynamic loss scaling (GradScaler, train.py:185-198)")
@@ -99,6 +102,12 @@ def build_criterion(args, background=255):
     return (ce, focal()) if args.criterion == "CE_Focal" else ce
 
 
+def check_optimizer(args):
+    """config.optimizer names the HIP path implements (train.py:114-135); other names raise."""
+    if args.optimizer not in OPTIMIZERS:
+        raise NotImplementedError(f"optimizer {args.optimizer} (on the HIP path: {', '.join(OPTIMIZERS)})")
+
+
 def resolve_precision(args):
     """(compute dtype, dynamic loss scaling on?).  The reference runs fp16 only under autocast
     with a GradScaler (train.py:185-198), so fp16 storage always turns loss scaling on, as in
@@ -114,8 +123,7 @@ def main(argv=None):
         seed = engine.local_rank if engine.distributed else args.seed
         torch.manual_seed(seed)
         criterion = build_criterion(args)
-        if args.optimizer != "AdamW":
-            raise NotImplementedError(f"optimizer {args.optimizer} (only AdamW is on the HIP path)")
+        check_optimizer(args)
         if not torch.cuda.is_available():
             raise RuntimeError("train.py runs the HIP path and needs a GPU")
         dev = torch.device("cuda", engine.local_rank)
@@ -141,7 +149,7 @@ def main(argv=None):
             train_loader, train_sampler = get_train_loader(engine, dataset, config)
 
         from rgbx_semantic_segmentation_amd.models.builder import EncoderDecoder
-        from rgbx_semantic_segmentation_amd.optim import FusedAdamW, GradScaler
+        from rgbx_semantic_segmentation_amd.optim import FusedAdamW, FusedSGD, GradScaler
         from rgbx_semantic_segmentation_amd import dist as cdist
 
         norm = torch.nn.SyncBatchNorm if engine.distributed else torch.nn.BatchNorm2d
@@ -156,8 +164,12 @@ def main(argv=None):
             cdist.broadcast_parameters(model, group)
             sync = cdist.BucketedGradSync(model.store, group)
             model.backbone.grad_sync = sync    # segment all-reduces overlap the backward
-        optimizer = FusedAdamW(model, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay,
-                               grad_sync=sync)
+        if args.optimizer == "SGDM":
+            optimizer = FusedSGD(model, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                                 grad_sync=sync)
+        else:
+            optimizer = FusedAdamW(model, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay,
+                                   grad_sync=sync)
         total_iteration = args.nepochs * args.niters_per_epoch
         lr_policy = WarmUpPolyLR(args.lr, args.lr_power, total_iteration, args.niters_per_epoch * args.warm_up_epoch)
 
