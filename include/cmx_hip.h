@@ -414,6 +414,29 @@ int cmx_aug_finalize(const uint8_t* rgb, const uint8_t* x, const uint8_t* gt, in
 int cmx_seg_window_accumulate(const float* s1, const float* s2, float* acc, int K, int ch, int cw, int m0, int m1, int m2, int m3, int PH, int PW, int sy, int sx, hipStream_t stream);
 int cmx_seg_argmax_confusion(const float* score, int K, int64_t HW, const void* label, int label_dtype, int n_cl, int* pred, int64_t* hist, int64_t* counts, hipStream_t stream);
 
+/* ---- MLPDecoderpp channel-attention gate (models/decoders/MLPDecoderpp.py:55-61 `attention`, applied at :81-82,
+ *      with the Dropout2d of :84-85) on the token-major fused map y (B, N, C), C % 8 == 0; a, dscale, pooled (B, C)
+ *      fp32.  The two-layer gate MLP between pool and scale is cmx_small_linear_fwd / cmx_act_fwd (B <= 8). */
+/* nn.AdaptiveAvgPool2d(1) (:56): pooled[b][c] = (1/N) sum_n y[b][n][c].  Per-chunk fp32 partials (chunks of at least
+ * cmx_se_chunk_rows() rows, cmx_se_pool_nchunk of them) in `workspace`, folded in chunk order by the last workgroup
+ * to arrive: deterministic, no float atomics.  tickets: cmx_se_pool_tickets(B, C) zeroed uint32 arrival counters
+ * owned by the caller (each launch leaves them zero; launches that may overlap need their own). */
+int cmx_se_chunk_rows(void);
+int cmx_se_pool_nchunk(int B, int N, int C);
+size_t cmx_se_pool_workspace(int B, int N, int C);
+size_t cmx_se_pool_tickets(int B, int C);
+int cmx_se_pool_fwd(const void* y, float* pooled, float* workspace, unsigned* tickets, int B, int N, int C, int dtype, hipStream_t stream);
+/* fused * attention (:82) and nn.Dropout2d (:85): out = y * a[b][c] * dscale[b][c]; dscale NULL (eval, p = 0): 1 */
+int cmx_se_scale_fwd(const void* y, const float* a, const float* dscale, void* out, int B, int N, int C, int dtype, hipStream_t stream);
+/* backward of :82 towards the gate: da[b][c] = dscale[b][c] * sum_n dout[b][n][c] y[b][n][c], written as
+ * cmx_se_bwd_nslice(B, N, C) slices da_part[s*B*C + b*C + c] -- the (dy_part, dy_nslice, dy_slice_stride = B*C,
+ * dy_row_stride = C) operand of cmx_small_linear_bwd, which sums them */
+int cmx_se_bwd_nslice(int B, int N, int C);
+int cmx_se_bwd_reduce(const void* dout, const void* y, const float* dscale, float* da_part, int B, int N, int C, int dtype, hipStream_t stream);
+/* backward of :82 and :56 towards the fused map: dy = dout * a[b][c] * dscale[b][c] + (1/N) sum_s dpool_part[s*slice_stride + b*C + c],
+ * dpool given as the nslice (<= 16) dx slices of cmx_small_linear_bwd (summed here, as cmx_frm_pool_bwd does) */
+int cmx_se_bwd_apply(const void* dout, const float* a, const float* dscale, const float* dpool_part, int nslice, int64_t slice_stride, void* dy, int B, int N, int C, int dtype, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

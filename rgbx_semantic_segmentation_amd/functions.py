@@ -1357,6 +1357,101 @@ def batchnorm(store, bn, x, training, res=None, act="none", dscale=None, rps=1, 
     return BatchNormF.apply(x, res, prm, training, act, dscale, rps, group, bn.weight)
 
 
+# ---------------------------------------------------------------------------- channel-attention gate
+_SE_TK: dict = {}
+
+
+def se_tickets(owner, x, B, C):
+    """Zeroed arrival counters of one gate's pooling (cmx_se_pool_tickets; each launch leaves them
+    zero), owned per (module -- ``owner`` is its anchor Parameter -- device, size) as pool_tickets
+    are.  Allocated at the first, eager call (the step runs eagerly before its capture)."""
+    key = (id(owner), x.device, B, C)
+    t = _SE_TK.get(key)
+    if t is None:
+        t = _SE_TK[key] = torch.zeros(max(1, K.query("cmx_se_pool_tickets", B, C)), dtype=torch.int32, device=x.device)
+    return t
+
+
+class SEGateF(Function):
+    """MLPDecoderpp's channel attention + Dropout2d (MLPDecoderpp.py:55-61, 81-85) on the fused map
+    y (B, N, C):  a = sigmoid(W2 GELU(W1 avgpool(y) + b1) + b2),  out = y * a * dscale.
+
+    Forward (5 launches): the pooling (cmx_se_pool_fwd, per-chunk partials folded by the last
+    block to arrive), the hidden GEMV, its GELU, the output GEMV with the sigmoid, the scale.
+    Backward (7 launches): da as per-chunk slices (cmx_se_bwd_reduce) that the sigmoid layer's
+    one-pass backward sums itself; its dx slices summed (cmx_partials_sum) for the GELU backward
+    on the saved pre-activation (cmx_small_linear_bwd derives act' from the saved OUTPUT, which
+    GELU does not allow); the hidden layer's backward; cmx_se_bwd_apply, which sums that layer's
+    dx slices as the pooled gradient.  The MLP runs on the fp32 master weights; its gradients
+    go straight into the flat gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, y, prm, dscale, anchor):
+        (W1, b1, W2, b2) = prm["w"]
+        B, N, C = y.shape
+        H = W1.shape[0]
+        dt = K.dtype_code(y)
+        f32 = dict(dtype=torch.float32, device=y.device)
+        pooled = torch.empty(B, C, **f32)
+        ws = K._ws(K.query("cmx_se_pool_workspace", B, N, C), y.device)
+        K.call("cmx_se_pool_fwd", K.ptr(y), K.ptr(pooled), K.ptr(ws), K.ptr(se_tickets(anchor, y, B, C)), B, N, C, dt,
+               K.stream())
+        z1 = torch.empty(B, H, **f32)
+        K.call("cmx_small_linear_fwd", K.ptr(pooled), K.ptr(W1), K.ptr(b1), K.ptr(z1), B, C, H, K.ACT["none"], K.stream())
+        h1 = torch.empty(B, H, **f32)
+        K.call("cmx_act_fwd", K.ptr(z1), K.ptr(h1), B * H, K.ACT["gelu"], 0, K.stream())
+        a = torch.empty(B, C, **f32)
+        K.call("cmx_small_linear_fwd", K.ptr(h1), K.ptr(W2), K.ptr(b2), K.ptr(a), B, H, C, K.ACT["sigmoid"], K.stream())
+        out = torch.empty_like(y)
+        K.call("cmx_se_scale_fwd", K.ptr(y), K.ptr(a), K.ptr(dscale), K.ptr(out), B, N, C, dt, K.stream())
+        ctx.save_for_backward(y, a, z1, pooled)
+        ctx.meta = (prm, dscale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, a, z1, pooled = ctx.saved_tensors
+        prm, dscale = ctx.meta
+        (W1, b1, W2, b2) = prm["w"]
+        (gW1, gb1, gW2, gb2) = prm["g"]
+        B, N, C = y.shape
+        H = W1.shape[0]
+        dt = K.dtype_code(y)
+        f32 = dict(dtype=torch.float32, device=y.device)
+        dout = _c(dout)
+        nda = K.query("cmx_se_bwd_nslice", B, N, C)
+        dap = torch.empty(nda, B, C, **f32)
+        K.call("cmx_se_bwd_reduce", K.ptr(dout), K.ptr(y), K.ptr(dscale), K.ptr(dap), B, N, C, dt, K.stream())
+        h1 = torch.empty(B, H, **f32)                 # GELU(z1) again: (B, C/4) values
+        K.call("cmx_act_fwd", K.ptr(z1), K.ptr(h1), B * H, K.ACT["gelu"], 0, K.stream())
+        ns = K.query("cmx_small_linear_nslice")
+        dh1p = torch.empty(ns, B, H, **f32)
+        K.call("cmx_small_linear_bwd", K.ptr(dap), nda, B * C, C, K.ptr(a), K.ptr(h1), K.ptr(W2), K.ptr(dh1p),
+               K.ptr(gW2), K.ptr(gb2), B, H, C, K.ACT["sigmoid"], 0, K.stream())
+        dh1 = torch.empty(B, H, **f32)
+        K.call("cmx_partials_sum", K.ptr(dh1p), K.ptr(dh1), 1, ns, B * H, 0, 1.0, K.stream())
+        dz1 = torch.empty(B, H, **f32)
+        K.call("cmx_act_bwd", K.ptr(dh1), K.ptr(z1), K.ptr(dz1), B * H, K.ACT["gelu"], 0, K.stream())
+        dpp = torch.empty(ns, B, C, **f32)
+        K.call("cmx_small_linear_bwd", K.ptr(dz1), 1, 0, H, K.ptr(z1), K.ptr(pooled), K.ptr(W1), K.ptr(dpp),
+               K.ptr(gW1), K.ptr(gb1), B, C, H, K.ACT["none"], 0, K.stream())
+        dy = torch.empty_like(y)
+        K.call("cmx_se_bwd_apply", K.ptr(dout), K.ptr(a), K.ptr(dscale), K.ptr(dpp), ns, B * C, K.ptr(dy), B, N, C, dt,
+               K.stream())
+        return dy, None, None, None
+
+
+def se_gate(store, att, y, dscale=None):
+    """SEGateF on y (B, N, C) with the head's ``attention`` Sequential (its two 1x1 convs at
+    [1] and [3], MLPDecoderpp.py:57,59)."""
+    f32 = lambda p: store.w(p, stacked=False, compute=False)
+    g = lambda p: store.g(p, stacked=False)
+    c1, c2 = att[1], att[3]
+    prm = {"w": (f32(c1.weight), f32(c1.bias), f32(c2.weight), f32(c2.bias)),
+           "g": (g(c1.weight), g(c1.bias), g(c2.weight), g(c2.bias))}
+    return SEGateF.apply(y, prm, dscale, c1.weight)
+
+
 # ---------------------------------------------------------------------------- decoder fuse
 def _adjoint_to(dZ, B, H1, W1, h, w, E):
     """up^T dZ: the bilinear adjoint of the (h, w) -> (H1, W1) upsample, (B, h*w, E) in dZ's
@@ -1384,47 +1479,70 @@ class DecoderFuseF(Function):
     Executed FLOPs: 38400 x 512 x 512 + low-res products instead of 38400 x 2048 x 512 (B2, bs=2);
     the step roofline keeps the reference's op-by-op count (flops.py)."""
 
+    # Wf column slot of the branches (c4, c3, c2, c1): the reference head concatenates [c4 | c3 | c2 | c1]
+    SLOTS = (0, 1, 2, 3)
+
     @staticmethod
     def forward(ctx, e4, e3, e2, e1, Wf, Wfg, bf, bfg, sizes, anchor):
-        B, N1, E = e1.shape
-        (H1, W1), hw = sizes[0], sizes[1:]        # hw: grids of c2, c3, c4
-        W = Wf[0]                                 # (E, 4E): column slots [c4 | c3 | c2 | c1]
-        zs, jobs = [], []
-        for slot, (e, (h, w)) in enumerate(zip((e4, e3, e2), (hw[2], hw[1], hw[0]))):
-            z = torch.empty(1, B * h * w, E, dtype=e.dtype, device=e.device)
-            jobs.append(dict(A=e.reshape(1, B * h * w, E), B=W[None, :, slot * E:(slot + 1) * E], C=z))
-            zs.append(z)
-        _gemm_group(jobs)                         # the three branch products: one launch
-        Z = torch.empty(B * N1, E, dtype=e1.dtype, device=e1.device)
-        Wc1 = W[:, 3 * E:]
-        K.call("cmx_decoder_fuse_fwd", K.ptr(_c(e1)), Wc1.data_ptr(), K.ptr(Z), K.ptr(bf), K.ptr(zs[0]), K.ptr(zs[1]),
-               K.ptr(zs[2]), B, H1, W1, hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, E, E,
-               W.stride(0), K.dtype_code(e1), K.stream())
-        ctx.save_for_backward(e4, e3, e2, e1, Wf)
-        ctx.meta = (Wfg, bfg, sizes)
-        return Z
+        return _decoder_fuse_fwd(ctx, DecoderFuseF.SLOTS, e4, e3, e2, e1, Wf, Wfg, bf, bfg, sizes)
 
     @staticmethod
     def backward(ctx, dZ):
-        e4, e3, e2, e1, Wf = ctx.saved_tensors
-        Wfg, bfg, sizes = ctx.meta
-        B, N1, E = e1.shape
-        (H1, W1), hw = sizes[0], sizes[1:]
-        dZ = _c(dZ).view(1, B * N1, E)
-        grads, jobs = [], []
-        for slot, (e, (h, w)) in enumerate(zip((e4, e3, e2), (hw[2], hw[1], hw[0]))):
-            dz = _adjoint_to(dZ, B, H1, W1, h, w, E).view(1, B * h * w, E)
-            sl = slice(slot * E, (slot + 1) * E)
-            g = torch.empty_like(dz)
-            jobs.append(dict(A=dz, B=Wf[:, :, sl].transpose(1, 2), C=g))
-            grads.append(g.view(e.shape))
-            _wgrad_into(dz, e.reshape(1, B * h * w, E), Wfg[:, :, sl])
-        e1f = e1.reshape(1, B * N1, E)
-        de1 = torch.empty_like(e1f)
-        jobs.append(dict(A=dZ, B=Wf[:, :, 3 * E:].transpose(1, 2), C=de1))
-        _wgrad_into(dZ, e1f, Wfg[:, :, 3 * E:], bfg)
-        _gemm_group(jobs)                         # the four branches' input gradients: one launch
-        return grads[0], grads[1], grads[2], de1.view(e1.shape), None, None, None, None, None, None
+        return _decoder_fuse_bwd(ctx, dZ)
+
+
+class DecoderFuseC1F(DecoderFuseF):
+    """DecoderFuseF for a head whose concat is [c1 | c2 | c3 | c4] (MLPDecoderpp.py:80): the same
+    launches, each branch on its own column slot of the conv."""
+    SLOTS = (3, 2, 1, 0)
+
+    @staticmethod
+    def forward(ctx, e4, e3, e2, e1, Wf, Wfg, bf, bfg, sizes, anchor):
+        return _decoder_fuse_fwd(ctx, DecoderFuseC1F.SLOTS, e4, e3, e2, e1, Wf, Wfg, bf, bfg, sizes)
+
+
+def _decoder_fuse_fwd(ctx, slots, e4, e3, e2, e1, Wf, Wfg, bf, bfg, sizes):
+    B, N1, E = e1.shape
+    (H1, W1), hw = sizes[0], sizes[1:]        # hw: grids of c2, c3, c4
+    W = Wf[0]                                 # (E, 4E): column slots[j] of branch j of (c4, c3, c2, c1)
+    zs, jobs = [], []
+    for j, (e, (h, w)) in enumerate(zip((e4, e3, e2), (hw[2], hw[1], hw[0]))):
+        slot = slots[j]
+        z = torch.empty(1, B * h * w, E, dtype=e.dtype, device=e.device)
+        jobs.append(dict(A=e.reshape(1, B * h * w, E), B=W[None, :, slot * E:(slot + 1) * E], C=z))
+        zs.append(z)
+    _gemm_group(jobs)                         # the three branch products: one launch
+    Z = torch.empty(B * N1, E, dtype=e1.dtype, device=e1.device)
+    Wc1 = W[:, slots[3] * E:(slots[3] + 1) * E]
+    K.call("cmx_decoder_fuse_fwd", K.ptr(_c(e1)), Wc1.data_ptr(), K.ptr(Z), K.ptr(bf), K.ptr(zs[0]), K.ptr(zs[1]),
+           K.ptr(zs[2]), B, H1, W1, hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, E, E,
+           W.stride(0), K.dtype_code(e1), K.stream())
+    ctx.save_for_backward(e4, e3, e2, e1, Wf)
+    ctx.meta = (Wfg, bfg, sizes, slots)
+    return Z
+
+
+def _decoder_fuse_bwd(ctx, dZ):
+    e4, e3, e2, e1, Wf = ctx.saved_tensors
+    Wfg, bfg, sizes, slots = ctx.meta
+    B, N1, E = e1.shape
+    (H1, W1), hw = sizes[0], sizes[1:]
+    dZ = _c(dZ).view(1, B * N1, E)
+    grads, jobs = [], []
+    for j, (e, (h, w)) in enumerate(zip((e4, e3, e2), (hw[2], hw[1], hw[0]))):
+        dz = _adjoint_to(dZ, B, H1, W1, h, w, E).view(1, B * h * w, E)
+        sl = slice(slots[j] * E, (slots[j] + 1) * E)
+        g = torch.empty_like(dz)
+        jobs.append(dict(A=dz, B=Wf[:, :, sl].transpose(1, 2), C=g))
+        grads.append(g.view(e.shape))
+        _wgrad_into(dz, e.reshape(1, B * h * w, E), Wfg[:, :, sl])
+    e1f = e1.reshape(1, B * N1, E)
+    de1 = torch.empty_like(e1f)
+    s1 = slice(slots[3] * E, (slots[3] + 1) * E)
+    jobs.append(dict(A=dZ, B=Wf[:, :, s1].transpose(1, 2), C=de1))
+    _wgrad_into(dZ, e1f, Wfg[:, :, s1], bfg)
+    _gemm_group(jobs)                         # the four branches' input gradients: one launch
+    return grads[0], grads[1], grads[2], de1.view(e1.shape), None, None, None, None, None, None
 
 
 # CMX_DECODER_FOLD=0: linear_c{1..4} as their own GEMMs ahead of DecoderFuseF (A/B switch)
@@ -1477,77 +1595,102 @@ class DecoderFoldF(Function):
     about 11 GFLOP forward + backward instead of 75 for DecoderFuseF on top of linear_c{1..4};
     the step roofline keeps the reference's op-by-op count (flops.py)."""
 
+    # Wf column slot of the branches (c4, c3, c2, c1); Wc, bc and the gradient views come in slot order
+    SLOTS = (0, 1, 2, 3)
+
     @staticmethod
     def forward(ctx, x4, x3, x2, x1, Wf, Wc, bf, bc, grads, sizes, anchor):
-        B, N1, C1 = x1.shape
-        E = Wf.shape[0]
-        (H1, W1), hw = sizes[0], sizes[1:]        # hw: grids of c2, c3, c4
-        xs = (x4, x3, x2, x1)                     # slot order of Wf's columns
-        Cs = [w.shape[1] for w in Wc]
-        Ms = [torch.empty(1, E, C, dtype=Wf.dtype, device=Wf.device) for C in Cs]
-        _gemm_group([dict(A=Wf[None, :, s * E:(s + 1) * E], B=Wc[s][None].transpose(1, 2), C=Ms[s], splitk=1)
-                     for s in range(4)])          # M_i = Wf_i Wc_i: one launch
-        b = torch.empty(E, dtype=torch.float32, device=Wf.device)
-        K.call("cmx_decoder_fold_bias", Wf.data_ptr(), Wf.stride(0), K.ptr(bf), *[K.ptr(t) for t in bc], K.ptr(b), E,
-               K.dtype_code(Wf), K.stream())
-        zs, jobs = [], []
-        for s, (h, w) in enumerate((hw[2], hw[1], hw[0])):
-            z = torch.empty(1, B * h * w, E, dtype=x1.dtype, device=x1.device)
-            jobs.append(dict(A=_c(xs[s]).reshape(1, B * h * w, Cs[s]), B=Ms[s], C=z))
-            zs.append(z)
-        _gemm_group(jobs)                         # the three low-resolution branch products: one launch
-        Z = torch.empty(B * N1, E, dtype=x1.dtype, device=x1.device)
-        if _up3_ok(E, [w for (_, w) in hw]):
-            # b + the three upsampled products in one pass, then the c1 GEMM with it as the residual
-            U = torch.empty(1, B * N1, E, dtype=x1.dtype, device=x1.device)
-            K.call("cmx_bilinear_up3_add", K.ptr(zs[0]), K.ptr(zs[1]), K.ptr(zs[2]), B, hw[2][0], hw[2][1], hw[1][0],
-                   hw[1][1], hw[0][0], hw[0][1], K.ptr(b), K.ptr(U), H1, W1, E, K.dtype_code(x1), K.stream())
-            K.gemm(_c(x1).view(1, B * N1, C1), Ms[3], Z.view(1, B * N1, E), residual=U)
-        else:
-            K.call("cmx_decoder_fuse_fwd", K.ptr(_c(x1)), K.ptr(Ms[3]), K.ptr(Z), K.ptr(b), K.ptr(zs[0]), K.ptr(zs[1]),
-                   K.ptr(zs[2]), B, H1, W1, hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, C1, C1, C1,
-                   K.dtype_code(x1), K.stream())
-        ctx.save_for_backward(*xs, Wf, *Wc, *Ms)
-        ctx.meta = (bc, grads, sizes, _adj3_ok(E, W1, [w for (_, w) in hw], x1.dtype))
-        return Z
+        return _decoder_fold_fwd(ctx, DecoderFoldF.SLOTS, x4, x3, x2, x1, Wf, Wc, bf, bc, grads, sizes)
 
     @staticmethod
     def backward(ctx, dZ):
-        t = ctx.saved_tensors
-        xs, Wf, Wc, Ms = t[:4], t[4], t[5:9], t[9:13]
-        bc, grads, sizes, adj3 = ctx.meta
-        B, N1, C1 = xs[3].shape
-        E = Wf.shape[0]
-        (H1, W1), hw = sizes[0], sizes[1:]
-        Cs = [w.shape[1] for w in Wc]
-        dZ = _c(dZ).view(1, B * N1, E)
-        offs = [0]
-        for C in Cs:
-            offs.append(offs[-1] + E * C)
-        dM = torch.empty(offs[-1], dtype=torch.float32, device=dZ.device)
-        gb = torch.empty(1, E, dtype=torch.float32, device=dZ.device)
-        if adj3:
-            # the three grids' bilinear adjoints from one read of dZ (cmx_bilinear_adjoint3)
-            dYs = [torch.empty(1, B * h * w, E, dtype=dZ.dtype, device=dZ.device) for (h, w) in (hw[2], hw[1], hw[0])]
-            ts = [torch.empty(B * H1 * w * E, dtype=torch.float32, device=dZ.device) for (h, w) in (hw[2], hw[1], hw[0])]
-            K.call("cmx_bilinear_adjoint3", K.ptr(dZ), *[K.ptr(t) for t in ts], *[K.ptr(y) for y in dYs], B, H1, W1,
-                   hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, K.dtype_code(dZ), K.stream())
-        dxs, jobs = [], []
-        for s in range(4):
-            if s == 3:
-                dY = dZ
-            elif adj3:
-                dY = dYs[s]
-            else:
-                dY = _adjoint_to(dZ, B, H1, W1, *hw[2 - s], E).view(1, -1, E)
-            x = xs[s].reshape(1, -1, Cs[s])
-            dx = torch.empty_like(x)
-            jobs.append(dict(A=dY, B=Ms[s].transpose(1, 2), C=dx))
-            dxs.append(dx.view(xs[s].shape))
-            _wgrad_into(dY, x, dM[offs[s]:offs[s + 1]].view(1, E, Cs[s]), gb if s == 3 else None)
-        _gemm_group(jobs)                         # the four branches' input gradients: one launch
-        deferred.after(lambda: _decoder_fold_chain(dM, gb, offs, Wf, Wc, bc, grads, Cs, E))
-        return (*dxs, None, None, None, None, None, None, None)
+        return _decoder_fold_bwd(ctx, dZ)
+
+
+class DecoderFoldC1F(DecoderFoldF):
+    """DecoderFoldF for a head whose concat is [c1 | c2 | c3 | c4] (MLPDecoderpp.py:80) and whose
+    projections are 1x1 convs (:42-45, the same products): the same launches, branch j of
+    (c4, c3, c2, c1) on column slot 3 - j of the conv; Wc, bc and the gradient views in slot order
+    (c1 first)."""
+    SLOTS = (3, 2, 1, 0)
+
+    @staticmethod
+    def forward(ctx, x4, x3, x2, x1, Wf, Wc, bf, bc, grads, sizes, anchor):
+        return _decoder_fold_fwd(ctx, DecoderFoldC1F.SLOTS, x4, x3, x2, x1, Wf, Wc, bf, bc, grads, sizes)
+
+
+def _decoder_fold_fwd(ctx, slots, x4, x3, x2, x1, Wf, Wc, bf, bc, grads, sizes):
+    B, N1, C1 = x1.shape
+    E = Wf.shape[0]
+    (H1, W1), hw = sizes[0], sizes[1:]        # hw: grids of c2, c3, c4
+    xs = (x4, x3, x2, x1)                     # branch order; branch j reads column slot slots[j] of Wf
+    Cs = [w.shape[1] for w in Wc]
+    Ms = [torch.empty(1, E, C, dtype=Wf.dtype, device=Wf.device) for C in Cs]
+    _gemm_group([dict(A=Wf[None, :, s * E:(s + 1) * E], B=Wc[s][None].transpose(1, 2), C=Ms[s], splitk=1)
+                 for s in range(4)])          # M_i = Wf_i Wc_i: one launch
+    b = torch.empty(E, dtype=torch.float32, device=Wf.device)
+    K.call("cmx_decoder_fold_bias", Wf.data_ptr(), Wf.stride(0), K.ptr(bf), *[K.ptr(t) for t in bc], K.ptr(b), E,
+           K.dtype_code(Wf), K.stream())
+    zs, jobs = [], []
+    for j, (h, w) in enumerate((hw[2], hw[1], hw[0])):
+        s = slots[j]
+        z = torch.empty(1, B * h * w, E, dtype=x1.dtype, device=x1.device)
+        jobs.append(dict(A=_c(xs[j]).reshape(1, B * h * w, Cs[s]), B=Ms[s], C=z))
+        zs.append(z)
+    _gemm_group(jobs)                         # the three low-resolution branch products: one launch
+    Z = torch.empty(B * N1, E, dtype=x1.dtype, device=x1.device)
+    if _up3_ok(E, [w for (_, w) in hw]):
+        # b + the three upsampled products in one pass, then the c1 GEMM with it as the residual
+        U = torch.empty(1, B * N1, E, dtype=x1.dtype, device=x1.device)
+        K.call("cmx_bilinear_up3_add", K.ptr(zs[0]), K.ptr(zs[1]), K.ptr(zs[2]), B, hw[2][0], hw[2][1], hw[1][0],
+               hw[1][1], hw[0][0], hw[0][1], K.ptr(b), K.ptr(U), H1, W1, E, K.dtype_code(x1), K.stream())
+        K.gemm(_c(x1).view(1, B * N1, C1), Ms[slots[3]], Z.view(1, B * N1, E), residual=U)
+    else:
+        K.call("cmx_decoder_fuse_fwd", K.ptr(_c(x1)), K.ptr(Ms[slots[3]]), K.ptr(Z), K.ptr(b), K.ptr(zs[0]), K.ptr(zs[1]),
+               K.ptr(zs[2]), B, H1, W1, hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, C1, C1, C1,
+               K.dtype_code(x1), K.stream())
+    ctx.save_for_backward(*xs, Wf, *Wc, *Ms)
+    ctx.meta = (bc, grads, sizes, _adj3_ok(E, W1, [w for (_, w) in hw], x1.dtype), slots)
+    return Z
+
+
+def _decoder_fold_bwd(ctx, dZ):
+    t = ctx.saved_tensors
+    xs, Wf, Wc, Ms = t[:4], t[4], t[5:9], t[9:13]
+    bc, grads, sizes, adj3, slots = ctx.meta
+    B, N1, C1 = xs[3].shape
+    E = Wf.shape[0]
+    (H1, W1), hw = sizes[0], sizes[1:]
+    Cs = [w.shape[1] for w in Wc]
+    dZ = _c(dZ).view(1, B * N1, E)
+    offs = [0]
+    for C in Cs:
+        offs.append(offs[-1] + E * C)
+    dM = torch.empty(offs[-1], dtype=torch.float32, device=dZ.device)
+    gb = torch.empty(1, E, dtype=torch.float32, device=dZ.device)
+    if adj3:
+        # the three grids' bilinear adjoints from one read of dZ (cmx_bilinear_adjoint3)
+        dYs = [torch.empty(1, B * h * w, E, dtype=dZ.dtype, device=dZ.device) for (h, w) in (hw[2], hw[1], hw[0])]
+        ts = [torch.empty(B * H1 * w * E, dtype=torch.float32, device=dZ.device) for (h, w) in (hw[2], hw[1], hw[0])]
+        K.call("cmx_bilinear_adjoint3", K.ptr(dZ), *[K.ptr(t) for t in ts], *[K.ptr(y) for y in dYs], B, H1, W1,
+               hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, K.dtype_code(dZ), K.stream())
+    dxs, jobs = [], []
+    for j in range(4):
+        s = slots[j]
+        if j == 3:
+            dY = dZ
+        elif adj3:
+            dY = dYs[j]
+        else:
+            dY = _adjoint_to(dZ, B, H1, W1, *hw[2 - j], E).view(1, -1, E)
+        x = xs[j].reshape(1, -1, Cs[s])
+        dx = torch.empty_like(x)
+        jobs.append(dict(A=dY, B=Ms[s].transpose(1, 2), C=dx))
+        dxs.append(dx.view(xs[j].shape))
+        _wgrad_into(dY, x, dM[offs[s]:offs[s + 1]].view(1, E, Cs[s]), gb if j == 3 else None)
+    _gemm_group(jobs)                         # the four branches' input gradients: one launch
+    deferred.after(lambda: _decoder_fold_chain(dM, gb, offs, Wf, Wc, bc, grads, Cs, E))
+    return (*dxs, None, None, None, None, None, None, None)
 
 
 def _decoder_fold_chain(dM, gb, offs, Wf, Wc, bc, grads, Cs, E):

@@ -36,6 +36,7 @@ import torch.nn as nn
 from .. import functions as F
 from .. import kernels as K
 from ..params import ParamStore
+from .decoders import MLPDecoder, MLPDecoderpp
 from .decoders.MLPDecoder import DecoderHead
 from .encoders.dual_segformer import BACKBONES, MIT_SPECS, load_dualpath_model
 
@@ -67,6 +68,9 @@ def backward_segment(name: str) -> int:
         return 3 - int(m.group(1))
     return 0
 
+
+# cfg.decoder (builder.py:154-161 of the reference) -> decode head class
+DECODERS = {"MLPDecoder": MLPDecoder.DecoderHead, "MLPDecoderpp": MLPDecoderpp.DecoderHead}
 
 SUPPORTED_CRITERIA = ("nn.CrossEntropyLoss(reduction='mean'[, weight=w]), FocalLoss(reduction='mean', gamma == 0 or "
                       "gamma >= 1), FocalLoss2d(reduction='mean'[, weight=w]) and CE_Focal = the tuple "
@@ -133,8 +137,8 @@ class EncoderDecoder(nn.Module):
             raise NotImplementedError(f"backbone {backbone!r}: only the MiT family (mit_b0..b5) is on the "
                                       "CMX hot path")
         decoder = _get(cfg, "decoder", "MLPDecoder")
-        if decoder != "MLPDecoder":
-            raise NotImplementedError(f"decoder {decoder!r}: only MLPDecoder is on the CMX hot path")
+        if decoder not in DECODERS:
+            raise NotImplementedError(f"decoder {decoder!r}: only {' and '.join(DECODERS)} are on the CMX hot path")
         # config.py:57-58 selects the rectify / fusion blocks (dual_segformer.py:316-329: 'FRM' / 'FFM'
         # the originals, any other value the improved IFRM / IFFM, as there)
         frm = _get(cfg, "feature_rectify_module", "FRM")
@@ -150,8 +154,8 @@ class EncoderDecoder(nn.Module):
         self.backbone = BACKBONES[backbone](norm_fuse=norm_layer, frm=frm, ffm=ffm)
         self.aux_head = None
         self.num_classes = int(_get(cfg, "num_classes", 40))
-        self.decode_head = DecoderHead(in_channels=self.channels, num_classes=self.num_classes,
-                                       norm_layer=norm_layer, embed_dim=int(_get(cfg, "decoder_embed_dim", 512)))
+        self.decode_head = DECODERS[decoder](in_channels=self.channels, num_classes=self.num_classes,
+                                             norm_layer=norm_layer, embed_dim=int(_get(cfg, "decoder_embed_dim", 512)))
         self.bn_eps = float(_get(cfg, "bn_eps", 1e-3))
         self.bn_momentum = float(_get(cfg, "bn_momentum", 0.1))
         dt = _get(cfg, "compute_dtype", None)

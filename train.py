@@ -35,11 +35,13 @@ logger = get_logger()
 
 CRITERIA = ("CrossEntropyLoss", "FocalLoss", "FocalLoss2d", "CE_Focal")
 OPTIMIZERS = ("AdamW", "SGDM")
+DECODERS = ("MLPDecoder", "MLPDecoderpp")
 
 
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--backbone", default="mit_b2")
+    p.add_argument("--decoder", default="MLPDecoder", choices=DECODERS, help="config.decoder (config.py:51)")
     p.add_argument("--num-classes", type=int, default=40)
     p.add_argument("--height", type=int, default=480)
     p.add_argument("--width", type=int, default=640)
@@ -154,7 +156,7 @@ def main(argv=None):
 
         norm = torch.nn.SyncBatchNorm if engine.distributed else torch.nn.BatchNorm2d
         dtype, loss_scaling = resolve_precision(args)
-        cfg = dict(backbone=args.backbone, num_classes=args.num_classes, compute_dtype=dtype,
+        cfg = dict(backbone=args.backbone, decoder=args.decoder, num_classes=args.num_classes, compute_dtype=dtype,
                    decoder_embed_dim=512)
         model = EncoderDecoder(cfg, criterion=criterion, norm_layer=norm).to(dev)
         sync = None
