@@ -10,10 +10,6 @@
 
 namespace {
 
-__device__ __forceinline__ void src_index(int dst, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
-  cmx_bilin_src(dst, scale, in, i0, i1, l0, l1);
-}
-
 // in (NB, Hi, Wi, C) dense; out pixel p at out + ((n*Ho + y)*Wo + x)*ops + c
 template <typename T>
 __global__ void bilinear_fwd_nhwc_kernel(const T* __restrict__ in, T* __restrict__ out, int NB, int Hi, int Wi, int Ho,
@@ -29,8 +25,8 @@ __global__ void bilinear_fwd_nhwc_kernel(const T* __restrict__ in, T* __restrict
     const int n = pix / (Wo * Ho);
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
-    src_index(y, sh, Hi, y0, y1, ly0, ly1);
-    src_index(x, sw, Wi, x0, x1, lx0, lx1);
+    cmx_bilin_src(y, sh, Hi, y0, y1, ly0, ly1);
+    cmx_bilin_src(x, sw, Wi, x0, x1, lx0, lx1);
     const T* base = in + (long)n * Hi * Wi * C + ch * V;
     float a[V], b[V], c[V], d[V], o[V];
     load_vec<T>(base + ((long)y0 * Wi + x0) * C, a);
@@ -55,8 +51,8 @@ __global__ void bilinear_fwd_nchw_kernel(const T* __restrict__ in, float* __rest
     const int n = i / (Wo * Ho * C);
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
-    src_index(y, sh, Hi, y0, y1, ly0, ly1);
-    src_index(x, sw, Wi, x0, x1, lx0, lx1);
+    cmx_bilin_src(y, sh, Hi, y0, y1, ly0, ly1);
+    cmx_bilin_src(x, sw, Wi, x0, x1, lx0, lx1);
     const T* base = in + (long)n * Hi * Wi * C + c;
     const float a = to_f32(base[((long)y0 * Wi + x0) * C]), b = to_f32(base[((long)y0 * Wi + x1) * C]);
     const float cc = to_f32(base[((long)y1 * Wi + x0) * C]), d = to_f32(base[((long)y1 * Wi + x1) * C]);
@@ -85,7 +81,7 @@ __global__ void bilinear_adj_kernel(const TI* __restrict__ in, TO* __restrict__ 
     for (int o = olo; o <= ohi; ++o) {
       int i0, i1;
       float l0, l1;
-      src_index(o, scale, Li, i0, i1, l0, l1);
+      cmx_bilin_src(o, scale, Li, i0, i1, l0, l1);
       float w = 0.f;
       if (i0 == i) w += l0;
       if (i1 == i) w += l1;
@@ -117,7 +113,7 @@ __global__ __launch_bounds__(256) void bilinear_adj8_kernel(const TI* __restrict
     for (int o = olo; o <= ohi; ++o) {
       int i0, i1;
       float l0, l1;
-      src_index(o, scale, Li, i0, i1, l0, l1);
+      cmx_bilin_src(o, scale, Li, i0, i1, l0, l1);
       float w = 0.f;
       if (i0 == i) w += l0;
       if (i1 == i) w += l1;
@@ -174,7 +170,7 @@ __global__ __launch_bounds__(256) void up3_add_kernel(const T* __restrict__ z0, 
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     if (q < nsrc) {
-      src_index(Y, (float)hs[q] / H, hs[q], rowa[q], rowb[q], wla[q], wlb[q]);
+      cmx_bilin_src(Y, (float)hs[q] / H, hs[q], rowa[q], rowb[q], wla[q], wlb[q]);
     } else {
       rowa[q] = rowb[q] = 0;
       wla[q] = wlb[q] = 0.f;
@@ -232,7 +228,7 @@ __global__ __launch_bounds__(256) void up3_add_kernel(const T* __restrict__ z0, 
       if (q >= nsrc) continue;
       int x0, x1;
       float l0, l1;
-      src_index(x, (float)ws[q] / W, ws[q], x0, x1, l0, l1);
+      cmx_bilin_src(x, (float)ws[q] / W, ws[q], x0, x1, l0, l1);
       const float4* p0 = reinterpret_cast<const float4*>(srow + off[q] + x0 * U3_CS + v8);
       const float4* p1 = reinterpret_cast<const float4*>(srow + off[q] + x1 * U3_CS + v8);
       const float4 a0 = p0[0], a1 = p0[1], b0 = p1[0], b1 = p1[1];
@@ -293,7 +289,7 @@ __global__ __launch_bounds__(256) void adj3_x_kernel(const T* __restrict__ dz, f
       if (o < W) {
         int i0, i1;
         float l0, l1;
-        src_index(o, scale, wsz[q], i0, i1, l0, l1);
+        cmx_bilin_src(o, scale, wsz[q], i0, i1, l0, l1);
         if (i0 == i) wgt += l0;
         if (i1 == i) wgt += l1;
       }
@@ -361,7 +357,7 @@ __global__ __launch_bounds__(256) void adj3_y_kernel(const float* __restrict__ t
     for (int o = olo; o <= ohi; ++o) {
       int i0, i1;
       float l0, l1;
-      src_index(o, scale, hs, i0, i1, l0, l1);
+      cmx_bilin_src(o, scale, hs, i0, i1, l0, l1);
       const float wgt = (i0 == y ? l0 : 0.f) + (i1 == y ? l1 : 0.f);
       if (wgt != 0.f) {
         const float* r = t + (((long)b * H + o) * ws + i) * C + v8;

@@ -1,425 +1,23 @@
-// Final upsample + the loss family beside plain CrossEntropyLoss, on the ce_cells scheme of
-// ce_fused.hip (forward: loss partials + the unscaled fp32 bilinear adjoint of the per-pixel
-// gradient at low resolution, in ONE pass over the full-resolution pixels; the backward is
-// cmx_upsample_ce_bwd_scale, unchanged).  No full-resolution tensor is ever materialised.
-//
-// With z = the x4 bilinear upsample (align_corners=False) of the low-res logits, p = softmax(z),
-// y = the pixel's label, eps = 1e-8:
-//   kind 0  nn.CrossEntropyLoss(weight=w)       l = w_y * -log p_y            norm = sum w_y
-//           (train.py:72-73 with a class weight)  dl/dz_j = w_y (p_j - [j = y])
-//   kind 1  FocalLoss2d (utils/loss_opr.py:12-23) l = -w_y (1 - p_y)^2 log p_y  norm = sum w_y
-//           dl/dz_j = c (p_j - [j = y]),  c = w_y ((1 - p_y)^2 - 2 p_y (1 - p_y) log p_y)
-//   kind 2  ce_scale * CE + focal_scale * FocalLoss (utils/loss_opr.py:158-202; CE_Focal,
-//           builder.py:246-247, is (1, 0.2); pure FocalLoss is (0, 1))         norm = n_valid
-//           focal l = -sum_k a_k x_k^gamma log(y_k + eps), (x, y, a)_k = (1 - p, p, alpha) at k = y,
-//           (p, 1 - p, 1 - alpha) elsewhere; u_k = dl/dp_k; dl/dz_j = p_j (u_j - sum_k u_k p_k).
-//           Labels are clamped to [0, K) and only label == ignore is invalid, as FocalLoss does.
-// Kinds 0 and 1 are the CE gradient times one scalar per pixel; kind 2 needs p_k of every class
-// twice (sum_k u_k p_k, then the gradient): both passes recompute it from the run's two
-// row-interpolated columns, as ce_cells' own two passes do.
-#include "cmx_common.h"
-
-namespace {
-
-constexpr int KF = 40;                            // classes held in LDS, as ce_fused.hip
-constexpr int CT_Y = 6, CT_X = 8;                 // low-res tile of a workgroup
-constexpr int CT_R = 4 * CT_Y + 4;                // full-res footprint rows
-constexpr int CT_C = CT_X + 1;                    // runs per footprint row
-constexpr int CT_NT = 256;
-static_assert(CT_R * CT_C <= CT_NT, "one run per thread");
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.69314718055994531f;
-constexpr float FEPS = 1e-8f;
-
-enum { LK_WCE = 0, LK_FL2D = 1, LK_FOCAL = 2 };
-// gamma paths of kind 2: integer powers for 0, 1, 2, 4; GP_GEN = exp2(gamma * log2 x), gamma > 1
-enum { GP_GEN = -1 };
-
-// x^(gamma - 1) and x^gamma for x in [0, 1]
-template <int GP>
-__device__ __forceinline__ void focal_pow(float x, float gamma, float& xg1, float& xg) {
-  if constexpr (GP == 0) {
-    xg1 = 0.f;                                    // only ever multiplied by gamma = 0
-    xg = 1.f;
-  } else if constexpr (GP == 1) {
-    xg1 = 1.f;
-    xg = x;
-  } else if constexpr (GP == 2) {
-    xg1 = x;
-    xg = x * x;
-  } else if constexpr (GP == 4) {
-    const float x2 = x * x;
-    xg1 = x2 * x;
-    xg = x2 * x2;
-  } else {
-    xg1 = __builtin_amdgcn_exp2f((gamma - 1.f) * __builtin_amdgcn_logf(x));   // x = 0: exp2(-inf) = 0
-    xg = xg1 * x;
-  }
-}
-
-// one class of one pixel: e = exp2(z_k - shift), sv = sum_k e, inv = 1 / sv (0: invalid pixel),
-// tgt = (k == y).  p, u = dl/dp_k, lt = the class's term of l.  1 - p is formed as (sv - e) / sv:
-// no rounding of p enters it (sv >= e: sv is a sum of non-negative terms that include e).
-template <int GP>
-__device__ __forceinline__ void focal_class(float e, float sv, float inv, bool tgt, float gamma, float alpha,
-                                            float& p, float& u, float& lt) {
-  p = e * inv;
-  const float q = fmaxf(sv - e, 0.f) * inv;
-  const float x = tgt ? q : p, ye = (tgt ? p : q) + FEPS;
-  const float as = tgt ? alpha : alpha - 1.f;     // u = as (gamma x^(gamma-1) log ye - x^gamma / ye)
-  const float an = tgt ? -alpha : alpha - 1.f;    // lt = an x^gamma log ye
-  const float L = __builtin_amdgcn_logf(ye) * LN2;
-  const float r = __builtin_amdgcn_rcpf(ye);
-  float xg1, xg;
-  focal_pow<GP>(x, gamma, xg1, xg);
-  if constexpr (GP == 0) u = -as * r;
-  else u = as * __builtin_fmaf(gamma * xg1, L, -xg * r);
-  lt = an * xg * L;
-}
-
-// The ce_cells scheme (ce_fused.hip): a workgroup owns a CT_Y x CT_X low-res tile of adj, a thread
-// one run of 4 full-res pixels that share their two low-res columns; class-major LDS image of the
-// logits tile + halo, x-adjoint in registers, y-adjoint through LDS, one fixed summation order.
-//   part[2 blk] = sum of l over the valid pixels the tile owns, part[2 blk + 1] = their normaliser
-//   adj (B, h, w, K) fp32 = bilinear adjoint of dl/dz, unscaled
-template <typename T, int LK, int GP>
-__global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits, const int64_t* __restrict__ label,
-                                                    const float* __restrict__ cw, float* __restrict__ dst,
-                                                    float* __restrict__ part, int h, int w, int H, int W, int K,
-                                                    int ignore, float gamma, float alpha, float cs, float fs,
-                                                    int tiles_x, int tiles_y) {
-  constexpr int LH = CT_Y + 2, LW = CT_X + 2, LP = LH * LW;   // low-res tile + 1-pixel halo
-  constexpr int KP = KF + 1;                                   // odd pitch of the column sums
-  __shared__ float lg[KF * LP];                                // class-major [k][row][col]
-  __shared__ float t1[CT_R * CT_X * KP + KP];                  // x-adjoint [row][col][k] + a spare row
-  __shared__ float wtab[CT_Y][8];                              // y-adjoint weights
-  __shared__ float red[2][CT_NT / 64];
-  const int t = threadIdx.x;
-  const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
-  const int y0 = by * CT_Y, x0 = bx * CT_X;
-  const int ny = min(CT_Y, h - y0), nx = min(CT_X, w - x0);
-  const float sh = (float)h / H, sw = (float)w / W;
-  const int ri = t / CT_C, c = t % CT_C;          // the thread's run: footprint row, cell
-  const bool act = ri < CT_R;
-  const int Y = 4 * y0 - 2 + ri, X0 = 4 * (x0 + c) - 2;
-  const bool rowin = act && Y >= 0 && Y < H;
-  // global loads first, all unconditional (an out-of-range element reads an in-range one and is
-  // replaced by a select), so they are in flight together
-  long lab[4];
-  bool labok[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int X = X0 + j;
-    labok[j] = rowin && X >= 0 && X < W;
-    lab[j] = label[labok[j] ? ((long)b * H + Y) * W + X : (long)b * H * W];
-  }
-  const T* base = logits + (long)b * h * w * K;
-  constexpr int NL = (LP * KF + CT_NT - 1) / CT_NT;
-  float v[NL];
-  bool vok[NL];
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-    const int e = t + i * CT_NT;
-    const int k = e % K, px = e / K;                // coalesced along k
-    const int yy = y0 - 1 + px / LW, xx = x0 - 1 + px % LW;
-    vok[i] = e < LP * K && yy >= 0 && yy < h && xx >= 0 && xx < w;
-    v[i] = to_f32(base[vok[i] ? ((long)yy * w + xx) * K + k : 0]);
-  }
-#pragma unroll
-  for (int i = 0; i < NL; ++i) v[i] = vok[i] ? v[i] : 0.f;
-  if (t < CT_Y * 8) {                             // low-res row y0 + yl from footprint row 4 yl + jj
-    const int yl = t >> 3, r = 4 * yl + (t & 7);
-    int ya, yb;
-    float wa, wb;
-    cmx_bilin_src(4 * y0 - 2 + r, sh, h, ya, yb, wa, wb);
-    wtab[yl][t & 7] = (4 * y0 - 2 + r >= 0 && 4 * y0 - 2 + r < H)
-                          ? (ya == y0 + yl ? wa : 0.f) + (yb == y0 + yl ? wb : 0.f) : 0.f;
-  }
-  int ya, yb;
-  float wya, wyb;
-  cmx_bilin_src(Y, sh, h, ya, yb, wya, wyb);      // rows outside the image: no valid pixel uses them
-  // the 4 pixels' weights on the run's columns x0 + c - 1 (tile column c) and x0 + c (c + 1);
-  // lv = the class of a valid pixel, -1 otherwise
-  const int xl = x0 + c - 1, xr = x0 + c;
-  float cl[4], cr[4];
-  int lv[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    int i0, i1;
-    float l0, l1;
-    cmx_bilin_src(X0 + j, sw, w, i0, i1, l0, l1);
-    cl[j] = (i0 == xl ? l0 : 0.f) + (i1 == xl ? l1 : 0.f);
-    cr[j] = (i0 == xr ? l0 : 0.f) + (i1 == xr ? l1 : 0.f);
-    if constexpr (LK == LK_FOCAL)                 // FocalLoss: clamp(label, 0, K - 1), invalid only at ignore
-      lv[j] = (labok[j] && lab[j] != ignore) ? (int)(lab[j] < 0 ? 0L : (lab[j] > K - 1 ? (long)(K - 1) : lab[j])) : -1;
-    else                                          // NLLLoss: as the CE kernels
-      lv[j] = (labok[j] && lab[j] >= 0 && lab[j] < K && lab[j] != ignore) ? (int)lab[j] : -1;
-  }
-  // class weights of the run's pixels (kinds 0, 1; NULL = 1): K floats, cached
-  float wy[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) wy[j] = (LK != LK_FOCAL && cw != nullptr) ? cw[lv[j] >= 0 ? lv[j] : 0] : 1.f;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-    const int e = t + i * CT_NT;
-    if (e < LP * K) lg[(e % K) * LP + e / K] = v[i];
-  }
-  // classes K .. KF - 1: a very negative logit (exp2 -> 0 exactly, maxima unchanged), so the class
-  // loops below run KF iterations without a branch on K
-  for (int e = t; e < (KF - K) * LP; e += CT_NT) lg[K * LP + e] = -1e30f;
-  __syncthreads();
-  // pass 1: the run's two row-interpolated columns per class (registers, log2 units), the bound
-  const float* la = lg + (min(max(ya - y0 + 1, 0), LH - 1)) * LW + c;
-  const float* lb = lg + (min(max(yb - y0 + 1, 0), LH - 1)) * LW + c;
-  const float wa2 = wya * LOG2E, wb2 = wyb * LOG2E;
-  float ml[KF], mr[KF];
-  float M = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < KF; ++k) {
-    ml[k] = __builtin_fmaf(wa2, la[k * LP], wb2 * lb[k * LP]);
-    mr[k] = __builtin_fmaf(wa2, la[k * LP + 1], wb2 * lb[k * LP + 1]);
-    M = fmaxf(M, fmaxf(ml[k], mr[k]));
-  }
-  // pass 2: the softmax denominators under the shared upper-bound shift (every pixel's logit is a
-  // convex combination of the two columns, so every exponent is <= 0)
-  float shv[4], sv[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    shv[j] = (cl[j] + cr[j]) * M;
-    sv[j] = 0.f;
-  }
-#pragma unroll
-  for (int k = 0; k < KF; ++k)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      sv[j] += __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -shv[j])));
-  // a pixel whose own maximum lies more than ~100 binary orders below the bound underflowed: redo
-  // it with its own maximum (the focal terms read 1 - p, so a flushed denominator would not do)
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (lv[j] >= 0 && !(sv[j] >= 0x1p-100f)) {
-      float m = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < KF; ++k) m = fmaxf(m, __builtin_fmaf(cl[j], ml[k], cr[j] * mr[k]));
-      shv[j] = m;
-      sv[j] = 0.f;
-#pragma unroll
-      for (int k = 0; k < KF; ++k)
-        sv[j] += __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -m)));
-    }
-  float inv[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) inv[j] = lv[j] >= 0 ? 1.f / sv[j] : 0.f;
-  // -log p_y of the valid pixels (the target logit: 4 LDS reads at the pixel's class)
-  float nll[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int q = (lv[j] >= 0 ? lv[j] : 0) * LP;
-    const float zl = __builtin_fmaf(cl[j], __builtin_fmaf(wa2, la[q], wb2 * lb[q]),
-                                    cr[j] * __builtin_fmaf(wa2, la[q + 1], wb2 * lb[q + 1]));
-    nll[j] = lv[j] >= 0 ? (shv[j] + __builtin_amdgcn_logf(sv[j]) - zl) * LN2 : 0.f;
-  }
-  // per pixel: pl = its loss, pn = its share of the normaliser, pc = the factor on (p - onehot)
-  float pl[4], pn[4], pc[4], S[4];
-  if constexpr (LK == LK_WCE) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      pc[j] = wy[j];
-      pl[j] = wy[j] * nll[j];
-      pn[j] = wy[j];
-    }
-  } else if constexpr (LK == LK_FL2D) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float p = __builtin_amdgcn_exp2f(-nll[j] * LOG2E), om = 1.f - p, lp = -nll[j];
-      pc[j] = wy[j] * om * __builtin_fmaf(-2.f * p, lp, om);
-      pl[j] = -wy[j] * om * om * lp;
-      pn[j] = wy[j];
-    }
-  } else {
-    // pass 2b: sum_k u_k p_k and the focal loss, over the K real classes (a padded class has
-    // p = 0 and contributes nothing for gamma >= 1; masked all the same: gamma = 0 leaves
-    // -(1 - alpha) log(1 + eps) per class)
-    float fl[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) S[j] = fl[j] = 0.f;
-#pragma unroll
-    for (int k = 0; k < KF; ++k) {
-      const bool real = k < K;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -shv[j])));
-        float p, u, lt;
-        focal_class<GP>(e, sv[j], inv[j], k == lv[j], gamma, alpha, p, u, lt);
-        S[j] += real ? u * p : 0.f;
-        fl[j] += real ? lt : 0.f;
-      }
-    }
-    // the sums are complete HERE: left to itself the compiler sinks their per-class tails towards
-    // their first use and keeps every class's operands live until then (scratch)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(S[j]), "+v"(fl[j]));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      pc[j] = cs;
-      pl[j] = __builtin_fmaf(fs, fl[j], cs * nll[j]);
-      pn[j] = 1.f;
-    }
-  }
-  {
-    // loss of the valid pixels this tile owns (full-res [4 y0, 4 y0 + 4 CT_Y) x [4 x0, 4 x0 + 4 CT_X))
-    float ls = 0.f, lc = 0.f;
-    const bool rown = Y >= 4 * y0 && Y < 4 * (y0 + CT_Y);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int X = X0 + j;
-      const bool own = lv[j] >= 0 && rown && X >= 4 * x0 && X < 4 * (x0 + CT_X);
-      ls += own ? pl[j] : 0.f;
-      lc += own ? pn[j] : 0.f;
-    }
-    ls = wave_sum(ls);
-    lc = wave_sum(lc);
-    if ((t & 63) == 0) {
-      red[0][t >> 6] = ls;
-      red[1][t >> 6] = lc;
-    }
-  }
-  // pass 3: the gradient's x-adjoint, the run's two column sums; the right column's go to LDS at
-  // once (lanes with nothing to write write the spare row), the left column's wait in registers
-  // for the barrier; then the -onehot terms at the pixels' classes
-  float* trow = t1 + (act ? ri : 0) * CT_X * KP;
-  float* wrow = (act && c < CT_X) ? trow + c * KP : t1 + CT_R * CT_X * KP;
-  float sl[KF];
-  if constexpr (LK == LK_FOCAL) {
-    // the same exponentials and target selects as pass 2b, on purpose: opaque copies of the shifts
-    // and classes keep the compiler from carrying pass 2b's per-class values (160 per thread and
-    // kind) across to here instead (scratch)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(shv[j]), "+v"(lv[j]));
-#pragma unroll
-    for (int k = 0; k < KF; ++k) {
-      float gl = 0.f, gr = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -shv[j])));
-        float p, u, lt;
-        focal_class<GP>(e, sv[j], inv[j], k == lv[j], gamma, alpha, p, u, lt);
-        const float g = p * __builtin_fmaf(fs, u - S[j], cs);   // invalid pixel, padded class: p = 0
-        gl = __builtin_fmaf(cl[j], g, gl);
-        gr = __builtin_fmaf(cr[j], g, gr);
-      }
-      wrow[k] = gr;                               // classes >= K: 0, never read
-      sl[k] = gl;
-    }
-  } else {
-    float al[4], ar[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      al[j] = cl[j] * inv[j] * pc[j];
-      ar[j] = cr[j] * inv[j] * pc[j];
-    }
-#pragma unroll
-    for (int k = 0; k < KF; ++k) {
-      float gl = 0.f, gr = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -shv[j])));
-        gl = __builtin_fmaf(al[j], e, gl);
-        gr = __builtin_fmaf(ar[j], e, gr);
-      }
-      wrow[k] = gr;
-      sl[k] = gl;
-    }
-  }
-  if (act && c < CT_X)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (lv[j] >= 0) trow[c * KP + lv[j]] -= cr[j] * pc[j];
-  __syncthreads();
-  if (act && c >= 1) {
-#pragma unroll
-    for (int k = 0; k < KF; ++k) trow[(c - 1) * KP + k] += sl[k];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (lv[j] >= 0) trow[(c - 1) * KP + lv[j]] -= cl[j] * pc[j];
-  }
-  __syncthreads();
-  if (t == 0) {
-    float a = 0.f, n = 0.f;
-#pragma unroll
-    for (int i = 0; i < CT_NT / 64; ++i) {
-      a += red[0][i];
-      n += red[1][i];
-    }
-    part[blockIdx.x * 2] = a;
-    part[blockIdx.x * 2 + 1] = n;
-  }
-  // y-adjoint: low-res row y takes full-res rows [4y - 2, 4y + 6) = footprint rows [4 yl, 4 yl + 8)
-  for (int e = t; e < CT_Y * CT_X * KF; e += CT_NT) {
-    const int k = e % KF, xq = (e / KF) % CT_X, yl = e / (KF * CT_X);
-    if (k >= K || xq >= nx || yl >= ny) continue;
-    const float* tc = t1 + (4 * yl * CT_X + xq) * KP + k;
-    float acc = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) acc = __builtin_fmaf(wtab[yl][jj], tc[jj * CT_X * KP], acc);
-    dst[((long)b * h * w + (long)(y0 + yl) * w + x0 + xq) * K + k] = acc;
-  }
-}
-
-// out[0] = loss = sum / norm, out[1] = 1 / norm, out[2] = norm.  ZERO_EMPTY (pure FocalLoss):
-// norm + eps in the quotients and loss 0 when nothing is valid; otherwise torch's mean (NaN then).
-template <bool ZERO_EMPTY>
-__global__ void loss_finalize_kernel(const float* __restrict__ part, int nblk, float* __restrict__ out) {
-  __shared__ double red[2][256];
-  double s = 0.0, c = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) { s += part[2 * i]; c += part[2 * i + 1]; }
-  red[0][threadIdx.x] = s;
-  red[1][threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double cnt = red[1][0];
-    if constexpr (ZERO_EMPTY) {
-      out[0] = cnt > 0 ? (float)(red[0][0] / (cnt + 1e-8)) : 0.f;
-      out[1] = cnt > 0 ? (float)(1.0 / (cnt + 1e-8)) : 0.f;
-    } else {
-      out[0] = cnt > 0 ? (float)(red[0][0] / cnt) : NAN;
-      out[1] = cnt > 0 ? (float)(1.0 / cnt) : 0.f;
-    }
-    out[2] = (float)cnt;
-  }
-}
-
-int loss_nblk(int B, int h, int w) { return B * ((h + CT_Y - 1) / CT_Y) * ((w + CT_X - 1) / CT_X); }
-
-template <int LK, int GP>
-int loss_cells_launch(const void* logits, const int64_t* label, const float* cw, float* adj, float* part, int B, int h,
-                      int w, int H, int W, int K, int ignore, float gamma, float alpha, float cs, float fs, int dtype,
-                      hipStream_t s) {
-  const int tx = (w + CT_X - 1) / CT_X, ty = (h + CT_Y - 1) / CT_Y;
-  CMX_DISPATCH(dtype, T, {
-    hipLaunchKernelGGL((loss_cells<T, LK, GP>), dim3(B * tx * ty), dim3(CT_NT), 0, s, (const T*)logits, label, cw, adj,
-                       part, h, w, H, W, K, ignore, gamma, alpha, cs, fs, tx, ty);
-  });
-  return CMX_OK;
-}
-
-}  // namespace
+// Final upsample + the loss family beside plain CrossEntropyLoss: the cells kernel of
+// loss_cells.h (where the criteria are stated) instantiated for kinds 0..2, the same template
+// ce_fused.hip instantiates for plain CE.  Forward: loss partials + the unscaled fp32 bilinear
+// adjoint of the per-pixel gradient at low resolution, in ONE pass over the full-resolution
+// pixels; the backward is cmx_upsample_ce_bwd_scale.  No full-resolution tensor is ever
+// materialised.
+#include "loss_cells.h"
 
 extern "C" {
 
 size_t cmx_upsample_loss_workspace(int B, int h, int w) {
   if (B <= 0 || h <= 0 || w <= 0) return 0;
-  return (size_t)loss_nblk(B, h, w) * 2 * sizeof(float);
+  return (size_t)loss_cells_nblk(B, h, w) * 2 * sizeof(float);
 }
 
 int cmx_upsample_loss_fwd_adj(const void* logits, const int64_t* label, const float* class_weight, float* adj,
                               float* out, float* workspace, int B, int h, int w, int H, int W, int K,
                               int ignore_index, int kind, float gamma, float alpha, float ce_scale, float focal_scale,
                               int dtype, hipStream_t s) {
-  CMX_REQUIRE(B > 0 && h > 0 && w > 0 && K > 0 && K <= KF && H == 4 * h && W == 4 * w, CMX_ERR_SHAPE,
+  CMX_REQUIRE(B > 0 && h > 0 && w > 0 && ce_tiled_ok(h, w, H, W, K), CMX_ERR_SHAPE,
               "upsample_loss_fwd_adj: needs H = 4h, W = 4w, K <= %d (K=%d, %dx%d -> %dx%d)", KF, K, h, w, H, W);
   CMX_REQUIRE(kind >= LK_WCE && kind <= LK_FOCAL, CMX_ERR_ARG,
               "upsample_loss_fwd_adj: kind %d (0 weighted CE, 1 FocalLoss2d, 2 ce_scale CE + focal_scale FocalLoss)",
@@ -427,11 +25,12 @@ int cmx_upsample_loss_fwd_adj(const void* logits, const int64_t* label, const fl
   CMX_REQUIRE(kind != LK_FOCAL || ((gamma == 0.f || gamma >= 1.f) && !class_weight), CMX_ERR_ARG,
               "upsample_loss_fwd_adj: FocalLoss takes gamma == 0 or gamma >= 1 (%g) and no class weight", (double)gamma);
   CMX_REQUIRE(logits && label && adj && out && workspace, CMX_ERR_ARG, "upsample_loss_fwd_adj: null operand");
-  const int nb = loss_nblk(B, h, w);
-  int st;
-#define CMX_LOSS_LAUNCH(LK, GP) \
-  st = loss_cells_launch<LK, GP>(logits, label, class_weight, adj, workspace, B, h, w, H, W, K, ignore_index, gamma, \
-                                 alpha, ce_scale, focal_scale, dtype, s)
+  const int nb = loss_cells_nblk(B, h, w);
+#define CMX_LOSS_LAUNCH(LK, GP)                                                                                       \
+  CMX_DISPATCH(dtype, T, {                                                                                            \
+    loss_cells_launch<T, LK, GP, true>((const T*)logits, label, class_weight, nullptr, nullptr, adj, workspace, B, h, \
+                                       w, H, W, K, ignore_index, gamma, alpha, ce_scale, focal_scale, s);             \
+  })
   if (kind == LK_WCE) CMX_LOSS_LAUNCH(LK_WCE, 0);
   else if (kind == LK_FL2D) CMX_LOSS_LAUNCH(LK_FL2D, 0);
   else if (gamma == 0.f) CMX_LOSS_LAUNCH(LK_FOCAL, 0);
@@ -440,7 +39,6 @@ int cmx_upsample_loss_fwd_adj(const void* logits, const int64_t* label, const fl
   else if (gamma == 4.f) CMX_LOSS_LAUNCH(LK_FOCAL, 4);
   else CMX_LOSS_LAUNCH(LK_FOCAL, GP_GEN);
 #undef CMX_LOSS_LAUNCH
-  if (st) return st;
   if (kind == LK_FOCAL && ce_scale == 0.f)
     hipLaunchKernelGGL(loss_finalize_kernel<true>, dim3(1), dim3(256), 0, s, workspace, nb, out);
   else

@@ -5,22 +5,15 @@
 // train.py:72-73), without materialising the full-resolution logits: each full-res pixel
 // interpolates its K logits from the 4 low-res neighbours (NHWC), computes log-softmax
 // and NLL, and writes the un-normalised gradient (softmax - onehot, 0 at ignored pixels).
-// A finalize kernel produces loss = sum / n_valid and 1 / n_valid on the device; the
-// backward is the separable bilinear adjoint of that gradient scaled by
+// The finalize kernel (loss_cells.h) produces loss = sum / n_valid and 1 / n_valid on the device;
+// the backward is the separable bilinear adjoint of that gradient scaled by
 // grad_output / n_valid (bilinear.hip), so the scaled 1/N never needs a host sync.
-#include "cmx_common.h"
+// For the decoder's exact x4 upsampling the entry points here launch ce_fused.hip's tiled forms
+// instead (declared in loss_cells.h): the loss-only forward, and the cells kernel with the
+// plain-CE criterion (cmx_upsample_ce_fwd_adj), whose backward is cmx_upsample_ce_bwd_scale.
+#include "loss_cells.h"
 
 namespace {
-
-__device__ __forceinline__ void src_index(int dst, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
-  float s = (dst + 0.5f) * scale - 0.5f;
-  if (s < 0.f) s = 0.f;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-  l0 = 1.f - l1;
-}
 
 constexpr int KMAX = 64;
 
@@ -44,8 +37,8 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const T* __restrict__ 
     }
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
-    src_index(y, sh, h, y0, y1, ly0, ly1);
-    src_index(x, sw, w, x0, x1, lx0, lx1);
+    cmx_bilin_src(y, sh, h, y0, y1, ly0, ly1);
+    cmx_bilin_src(x, sw, w, x0, x1, lx0, lx1);
     const T* base = logits + (long)b * h * w * K;
     const T* pa = base + ((long)y0 * w + x0) * K;
     const T* pb = base + ((long)y0 * w + x1) * K;
@@ -82,40 +75,11 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const T* __restrict__ 
   }
 }
 
-// out[0] = loss (sum / count), out[1] = 1 / count, out[2] = count
-__global__ void ce_finalize_kernel(const float* __restrict__ part, int nblk, float* __restrict__ out) {
-  __shared__ double red[2][256];
-  double s = 0.0, c = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) { s += part[2 * i]; c += part[2 * i + 1]; }
-  red[0][threadIdx.x] = s;
-  red[1][threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double cnt = red[1][0];
-    out[0] = cnt > 0 ? (float)(red[0][0] / cnt) : NAN;   // PyTorch: mean over zero valid pixels is NaN
-    out[1] = cnt > 0 ? (float)(1.0 / cnt) : 0.f;
-    out[2] = (float)cnt;
-  }
-}
-
 int ce_nblk(long total) {
   long nb = (total + 255) / 256;
   return (int)(nb < 2048 ? (nb ? nb : 1) : 2048);
 }
 }  // namespace
-
-// ce_fused.hip: LDS-tiled loss-only forward (grad == NULL)
-int ce_fwd_tiled_nblk(int B, int H, int W);
-bool ce_tiled_ok(int h, int w, int H, int W, int K);
-int ce_fwd_tiled_launch(const void* logits, const int64_t* label, float* part, int B, int h, int w, int H, int W,
-                        int K, int ignore, int dtype, hipStream_t s);
-int ce_cells_nblk(int B, int h, int w);
-int ce_cells_fwd_launch(const void* logits, const int64_t* label, float* adj, float* part, int B, int h, int w, int H,
-                        int W, int K, int ignore, int dtype, hipStream_t s);
 
 extern "C" {
 
@@ -134,7 +98,7 @@ int cmx_upsample_ce_fwd(const void* logits, const int64_t* label, void* grad, fl
     const int nbt = ce_fwd_tiled_nblk(B, H, W);
     const int st = ce_fwd_tiled_launch(logits, label, workspace, B, h, w, H, W, K, ignore_index, dtype, s);
     if (st) return st;
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, workspace, nbt, out);
+    hipLaunchKernelGGL(loss_finalize_kernel<false>, dim3(1), dim3(256), 0, s, workspace, nbt, out);
     return cmx_check_launch("upsample_ce_fwd");
   }
   const int nb = ce_nblk((long)B * H * W);
@@ -142,7 +106,7 @@ int cmx_upsample_ce_fwd(const void* logits, const int64_t* label, void* grad, fl
     hipLaunchKernelGGL(upsample_ce_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)logits, label, (T*)grad, workspace,
                        B, h, w, H, W, K, ignore_index);
   });
-  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, workspace, nb, out);
+  hipLaunchKernelGGL(loss_finalize_kernel<false>, dim3(1), dim3(256), 0, s, workspace, nb, out);
   return cmx_check_launch("upsample_ce_fwd");
 }
 
@@ -152,10 +116,10 @@ int cmx_upsample_ce_fwd_adj(const void* logits, const int64_t* label, float* adj
                             int h, int w, int H, int W, int K, int ignore_index, int dtype, hipStream_t s) {
   CMX_REQUIRE(B > 0 && adj && ce_tiled_ok(h, w, H, W, K), CMX_ERR_SHAPE,
               "upsample_ce_fwd_adj: needs H = 4h, W = 4w, K <= 40 (K=%d, %dx%d -> %dx%d)", K, h, w, H, W);
-  const int nb = ce_cells_nblk(B, h, w);
+  const int nb = loss_cells_nblk(B, h, w);
   const int st = ce_cells_fwd_launch(logits, label, adj, workspace, B, h, w, H, W, K, ignore_index, dtype, s);
   if (st) return st;
-  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, workspace, nb, out);
+  hipLaunchKernelGGL(loss_finalize_kernel<false>, dim3(1), dim3(256), 0, s, workspace, nb, out);
   return cmx_check_launch("upsample_ce_fwd_adj");
 }
 

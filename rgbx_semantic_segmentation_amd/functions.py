@@ -1711,6 +1711,14 @@ def _decoder_fold_chain(dM, gb, offs, Wf, Wc, bc, grads, Cs, E):
 
 
 # ---------------------------------------------------------------------------- final upsample + CE
+def _scale_adjoint(ctx, adj, dloss, out):
+    """The backward of the forward-adjoint losses: dlogits = adj * dloss / normaliser (out[1])."""
+    dl = torch.empty(ctx.lshape, dtype=ctx.ldtype, device=adj.device)
+    K.call("cmx_upsample_ce_bwd_scale", K.ptr(adj), K.ptr(dloss), K.ptr(out), K.ptr(dl), dl.numel(),
+           K.dtype_code(dl), K.stream())
+    return dl
+
+
 class UpsampleCEF(Function):
     """F.interpolate(logits, (H, W), bilinear) + CrossEntropyLoss(mean, ignore_index)
     (builder.py:233,249) fused; full-res logits are never materialised."""
@@ -1731,12 +1739,12 @@ class UpsampleCEF(Function):
             K.call("cmx_upsample_ce_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(adj), K.ptr(out), K.ptr(ws), B, h, w,
                    H, W, Kc, ignore, K.dtype_code(logits), K.stream())
             ctx.save_for_backward(adj, out, label)
-            ctx.fused, ctx.ignore, ctx.ldtype, ctx.lshape = "adj", ignore, logits.dtype, logits.shape
+            ctx.fused, ctx.ldtype, ctx.lshape = "adj", logits.dtype, logits.shape
             return out[0]
         K.call("cmx_upsample_ce_fwd", K.ptr(logits), K.ptr(label), K.ptr(grad), K.ptr(out), K.ptr(ws), B, h, w, H,
                W, Kc, ignore, K.dtype_code(logits), K.stream())
         ctx.save_for_backward(logits if fused else grad, out, label)
-        ctx.fused, ctx.ignore = fused, ignore
+        ctx.fused = fused
         ctx.dims = dims
         ctx.ldtype = logits.dtype
         ctx.lshape = logits.shape
@@ -1747,17 +1755,10 @@ class UpsampleCEF(Function):
         grad, out, label = ctx.saved_tensors
         dloss = _c(dloss.reshape(1).to(torch.float32))
         if ctx.fused == "adj":
-            dl = torch.empty(ctx.lshape, dtype=ctx.ldtype, device=grad.device)
-            K.call("cmx_upsample_ce_bwd_scale", K.ptr(grad), K.ptr(dloss), K.ptr(out), K.ptr(dl), dl.numel(),
-                   K.dtype_code(dl), K.stream())
-            return dl, None, None, None
+            return _scale_adjoint(ctx, grad, dloss, out), None, None, None
+        # the materialised gradient (a fused loss-only forward ran without needs_input_grad:
+        # autograd never comes here for it)
         B, h, w, H, W, Kc = ctx.dims
-        if ctx.fused:
-            logits = grad
-            dl = torch.empty(B, h * w, Kc, dtype=ctx.ldtype, device=logits.device)
-            K.call("cmx_upsample_ce_bwd", K.ptr(logits), K.ptr(label), K.ptr(dloss), K.ptr(out), K.ptr(dl), B, h, w,
-                   H, W, Kc, ctx.ignore, K.dtype_code(logits), K.stream())
-            return dl.view(ctx.lshape), None, None, None
         tmp = torch.empty(B * H, w, Kc, dtype=torch.float32, device=grad.device)
         K.call("cmx_bilinear_adjoint_1d", K.ptr(grad), K.ptr(tmp), B * H, W, w, Kc, W * Kc, Kc, 0, 0, 1.0,
                K.dtype_code(grad), 0, K.stream())
@@ -1806,10 +1807,7 @@ class UpsampleLossF(Function):
     def backward(ctx, dloss):
         adj, out = ctx.saved_tensors
         dloss = _c(dloss.reshape(1).to(torch.float32))
-        dl = torch.empty(ctx.lshape, dtype=ctx.ldtype, device=adj.device)
-        K.call("cmx_upsample_ce_bwd_scale", K.ptr(adj), K.ptr(dloss), K.ptr(out), K.ptr(dl), dl.numel(),
-               K.dtype_code(dl), K.stream())
-        return dl, None, None, None, None, None
+        return _scale_adjoint(ctx, adj, dloss, out), None, None, None, None, None
 
 
 def upsample_logits_nchw(logits, B, h, w, H, W, Kc):

@@ -60,7 +60,7 @@ FAMILIES = [
     ("BatchNorm (stats, fold, apply, bwd)", r"bn_"),
     ("FRM (pool, channel MLP, combine)", r"pool_|linear_fwd|linear_bwd|combine_|frm_|reduce_partials"),
     ("FFM context / cross attention", r"ffm_"),
-    ("upsample + CE", r"ce_|upsample"),
+    ("upsample + CE", r"ce_|upsample|loss_cells|loss_finalize"),
     ("bilinear (decoder fuse adjoint)", r"bilinear|adj3_|up3_"),
     ("im2col / col2im", r"im2col|col2im"),
     ("stage-1 patch embed (direct conv fwd, wgrad)", r"pe1_"),

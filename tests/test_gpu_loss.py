@@ -156,6 +156,63 @@ def test_containment(dev, name):
     check(name, shape, torch.bfloat16, out[0], dl, lc.expected(name, shape, torch.bfloat16))
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", lc.SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_plain_ce_equals_unweighted_kind0(dev, shape, dtype):
+    """cmx_upsample_ce_fwd_adj and cmx_upsample_loss_fwd_adj with kind 0 and a null weight give the
+    same bits in out (all three floats) and adj: the two criteria of the one cells kernel differ only
+    by multiplications with 1.0f and additions of +0.0f."""
+    from rgbx_semantic_segmentation_amd import kernels as Kn
+    from rgbx_semantic_segmentation_amd.functions import LOSS_WCE
+    B, h, w, K = shape
+    H, W = 4 * h, 4 * w
+    lg, lab = lc.make_inputs(shape)
+    x, labd = lg.to(dev, dtype).contiguous(), lab.to(dev)
+    adj = [torch.full((B, h, w, K), float("nan"), device=dev) for _ in range(2)]
+    out = [torch.full((3,), float("nan"), device=dev) for _ in range(2)]
+    ws = Kn._ws(max(Kn.query("cmx_upsample_ce_workspace", B, H, W), Kn.query("cmx_upsample_loss_workspace", B, h, w)),
+                dev)
+    Kn.call("cmx_upsample_ce_fwd_adj", Kn.ptr(x), Kn.ptr(labd), Kn.ptr(adj[0]), Kn.ptr(out[0]), Kn.ptr(ws), B, h, w,
+            H, W, K, lc.IGNORE, Kn.dtype_code(x), Kn.stream())
+    Kn.call("cmx_upsample_loss_fwd_adj", Kn.ptr(x), Kn.ptr(labd), 0, Kn.ptr(adj[1]), Kn.ptr(out[1]), Kn.ptr(ws), B,
+            h, w, H, W, K, lc.IGNORE, LOSS_WCE, 0.0, 0.0, 0.0, 0.0, Kn.dtype_code(x), Kn.stream())
+    torch.cuda.synchronize()
+    assert torch.isfinite(out[0]).all() and torch.isfinite(adj[0]).all()
+    assert torch.equal(out[0], out[1]), (out[0].tolist(), out[1].tolist())
+    assert torch.equal(adj[0], adj[1]), float((adj[0] - adj[1]).abs().max())
+
+
+def test_containment_plain_ce(dev):
+    """The plain-CE entry points at SHAPES[2] in bf16: cmx_upsample_ce_fwd_adj's fp32 adj and
+    cmx_upsample_ce_bwd's bf16 dlogits (the recompute backward's store in the logits' dtype) each sit
+    inside a NaN-filled allocation with guard rows, which come back bit-equal around a finite interior."""
+    from rgbx_semantic_segmentation_amd import kernels as Kn
+    shape = lc.SHAPES[2]
+    B, h, w, K = shape
+    H, W = 4 * h, 4 * w
+    lg, lab = lc.make_inputs(shape)
+    x, labd = lg.to(dev, torch.bfloat16).contiguous(), lab.to(dev)
+    n, guard = B * h * w * K, 3 * w * K
+    adj_buf = torch.full((n + 2 * guard,), float("nan"), device=dev)
+    dl_buf = torch.full((n + 2 * guard,), float("nan"), device=dev).to(torch.bfloat16)
+    adj, dl = adj_buf[guard:guard + n], dl_buf[guard:guard + n]
+    bits = [(buf, buf.view(it), buf.view(it).clone()) for buf, it in ((adj_buf, torch.int32), (dl_buf, torch.int16))]
+    out = torch.empty(3, device=dev)
+    ws = Kn._ws(Kn.query("cmx_upsample_ce_workspace", B, H, W), dev)
+    Kn.call("cmx_upsample_ce_fwd_adj", Kn.ptr(x), Kn.ptr(labd), adj.data_ptr(), Kn.ptr(out), Kn.ptr(ws), B, h, w, H,
+            W, K, lc.IGNORE, Kn.dtype_code(x), Kn.stream())
+    dloss = torch.full((1,), lc.DLOSS, device=dev)
+    Kn.call("cmx_upsample_ce_bwd", Kn.ptr(x), Kn.ptr(labd), Kn.ptr(dloss), Kn.ptr(out), dl.data_ptr(), B, h, w, H, W,
+            K, lc.IGNORE, Kn.dtype_code(x), Kn.stream())
+    torch.cuda.synchronize()
+    for buf, now, before in bits:
+        assert torch.equal(now[:guard], before[:guard]) and torch.equal(now[guard + n:], before[guard + n:])
+        assert torch.isfinite(buf[guard:guard + n]).all()
+    # the recompute backward is the scaled adjoint, rounded once to bf16
+    want = adj * (lc.DLOSS * out[1])
+    assert lc.relerr(dl.float(), want) < 2 * lc.TOL[torch.bfloat16]
+
+
 @pytest.mark.parametrize("name", list(lc.CRITERIA))
 def test_no_grad_loss_is_the_training_loss(dev, name):
     """Validation (torch.no_grad()) runs the same kernel: the loss equals the training forward's bit for bit."""
