@@ -239,6 +239,21 @@ int cmx_upsample_ce_bwd_scale(const float* adj, const float* dloss, const float*
  *              asserts on it). */
 size_t cmx_upsample_loss_workspace(int B, int h, int w);
 int cmx_upsample_loss_fwd_adj(const void* logits, const int64_t* label, const float* class_weight, float* adj, float* out, float* workspace, int B, int h, int w, int H, int W, int K, int ignore_index, int kind, float gamma, float alpha, float ce_scale, float focal_scale, int dtype, hipStream_t stream);
+/* ---- the same for dice_scale * DiceLoss(smooth) + ce_scale * CrossEntropyLoss (utils/loss_opr.py:103-156; DiceLoss
+ *      is (0, 1), DiceCELoss(alpha) is (1 - alpha, alpha); reduction 'mean'; H = 4h, W = 4w, K <= 40, else
+ *      CMX_ERR_SHAPE).  Dice is not a per-pixel function, so this is three launches: a statistics pass over the
+ *      pixels (per-block partials), a finalize that folds them per (image, class) in fp64 in a fixed order and writes
+ *      stats (B, K, 3) fp32 = [I = sum v p_k [y = k], P = sum v p_k, T = sum v [y = k]] and out = [loss, backward
+ *      factor, n_valid] -- the loss is complete there -- and the gradient pass, adj (B, h, w, K) fp32 = the bilinear
+ *      adjoint of dice_scale dL_dice/dz + ce_scale (p - onehot) / n_valid, final up to dloss: the backward is
+ *      cmx_upsample_ce_bwd_scale with out[1] = 1.  adj NULL: loss and stats only, the gradient pass is not launched.
+ *      v = (label != ignore_index), y = clamp(label, 0, K - 1), as FocalLoss.  Nothing valid: the Dice term is
+ *      exactly 0 with a zero gradient; with ce_scale != 0 the loss is NaN (torch's mean) and out[1] = 0.  smooth > 0
+ *      and scales >= 0, else CMX_ERR_ARG.  No floating-point atomics: bit-identical from run to run.
+ *      workspace: cmx_upsample_dice_workspace bytes = (blocks of the 6 x 8 low-res tiling x (3K + 2) partials +
+ *      B x (2K + 1) coefficients) fp32. */
+size_t cmx_upsample_dice_workspace(int B, int h, int w, int K);
+int cmx_upsample_dice_fwd_adj(const void* logits, const int64_t* label, float* adj, float* out, float* stats, float* workspace, int B, int h, int w, int H, int W, int K, int ignore_index, float ce_scale, float dice_scale, float smooth, int dtype, hipStream_t stream);
 
 /* ---- dense layers: batched MFMA GEMM with fused epilogues -----------------------------
  * Replaces every nn.Linear and 1x1 Conv2d of the path (dual_segformer.py:42-43, 87-96, 110;

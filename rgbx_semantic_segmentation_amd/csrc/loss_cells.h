@@ -19,6 +19,19 @@
 // LK_CE and kinds 0 and 1 are the CE gradient times one scalar per pixel; kind 2 needs p_k of every
 // class twice (sum_k u_k p_k, then the gradient): both passes recompute it from the run's two
 // row-interpolated columns, as the kernel's own passes 2 and 3 do.
+//
+// DiceLoss / DiceCELoss (utils/loss_opr.py:103-156; dice_fused.hip) is not a per-pixel function: with
+// v = (label != ignore), y = clamp(label, 0, K - 1) (FocalLoss's rule) and, per image b and class k,
+// I = sum v p_k [y = k], P = sum v p_k, T = sum v [y = k], U = P + T over the image's pixels,
+//   dice = (2 I + s) / (U + s),  DiceLoss = 1 - mean_(b,k) dice,
+//   d DiceLoss / dp_k = u_k = v (c[b,k] - [y = k] a[b,k]),  c = (2 I + s) / ((U + s)^2 B K),
+//   a = 2 / ((U + s) B K),  dl/dz_j = p_j (u_j - sum_k u_k p_k)  (kind 2's form).
+// Two criteria of the template serve it:
+//   LK_DSTAT  the statistics pass: per-block partials of I, P, T, the CE sum and the valid count over
+//             the pixels the tile owns; ends after pass 2, no adjoint (t1 is never touched)
+//   LK_DICE   the gradient pass, after dice_finalize_kernel made the coefficient table from the folded
+//             statistics: dst = the adjoint of dL_dice/dz + cen (p - onehot), cen = ce_scale / n_valid;
+//             the table (cw: per image c'[K], a'[K], cen; c', a' = dice_scale * c, a) is read from LDS
 #pragma once
 #include "cmx_common.h"
 
@@ -43,7 +56,8 @@ constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.69314718055994531f;
 constexpr float FEPS = 1e-8f;
 
 // LK_CE is internal: cmx_upsample_loss_fwd_adj's `kind` is 0..2
-enum { LK_CE = -1, LK_WCE = 0, LK_FL2D = 1, LK_FOCAL = 2 };
+enum { LK_CE = -1, LK_WCE = 0, LK_FL2D = 1, LK_FOCAL = 2, LK_DICE = 3, LK_DSTAT = 4 };
+template <int LK> constexpr bool lk_dice = LK == LK_DICE || LK == LK_DSTAT;
 // gamma paths of kind 2: integer powers for 0, 1, 2, 4; GP_GEN = exp2(gamma * log2 x), gamma > 1
 enum { GP_GEN = -1 };
 
@@ -51,6 +65,10 @@ enum { GP_GEN = -1 };
 inline bool ce_tiled_ok(int h, int w, int H, int W, int K) { return K > 0 && K <= KF && H == 4 * h && W == 4 * w; }
 
 inline int loss_cells_nblk(int B, int h, int w) { return B * ((h + CT_Y - 1) / CT_Y) * ((w + CT_X - 1) / CT_X); }
+// Dice: floats per block of the statistics partials [I[K], P[K], T[K], CE sum, valid count], and per
+// image of the coefficient table [c'[K], a'[K], cen]
+__host__ __device__ constexpr int dice_part_stride(int K) { return 3 * K + 2; }
+__host__ __device__ constexpr int dice_coef_stride(int K) { return 2 * K + 1; }
 
 // x^(gamma - 1) and x^gamma for x in [0, 1]
 template <int GP>
@@ -121,6 +139,8 @@ __device__ __forceinline__ float target_nll(const float* la, const float* lb, in
 //                (the backward only scales it: cmx_upsample_ce_bwd_scale)
 //   FWD = false: LK_CE only, the recompute backward: dst in T = the adjoint of
 //                (softmax - onehot) * dloss[0] * stats[1]
+//   LK_DSTAT:    part[dice_part_stride(K) blk ..] = the block's statistics partials; dst unused
+//   LK_DICE:     cw = the coefficient table; dst as FWD = true, final up to dloss; part unused
 // cw, gamma, alpha, cs, fs: the criterion's parameters (see the top); LK_CE reads none of them.
 template <typename T, int LK, int GP, bool FWD>
 __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits, const int64_t* __restrict__ label,
@@ -194,7 +214,7 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
     cmx_bilin_src(X0 + j, sw, w, i0, i1, l0, l1);
     cl[j] = (i0 == xl ? l0 : 0.f) + (i1 == xl ? l1 : 0.f);
     cr[j] = (i0 == xr ? l0 : 0.f) + (i1 == xr ? l1 : 0.f);
-    if constexpr (LK == LK_FOCAL)                 // FocalLoss: clamp(label, 0, K - 1), invalid only at ignore
+    if constexpr (LK == LK_FOCAL || lk_dice<LK>)  // FocalLoss: clamp(label, 0, K - 1), invalid only at ignore
       lv[j] = (labok[j] && lab[j] != ignore) ? (int)(lab[j] < 0 ? 0L : (lab[j] > K - 1 ? (long)(K - 1) : lab[j])) : -1;
     else                                          // NLLLoss
       lv[j] = (labok[j] && lab[j] >= 0 && lab[j] < K && lab[j] != ignore) ? (int)lab[j] : -1;
@@ -213,6 +233,26 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
   // classes K .. KF - 1: a very negative logit (exp2 -> 0 exactly, maxima unchanged), so the class
   // loops below run KF iterations without a test on K (a runtime test became a branch per class)
   for (int e = t; e < (KF - K) * LP; e += CT_NT) lg[K * LP + e] = -1e30f;
+  // Dice: the image's coefficients c'[k] at ctab[k], a'[k] at ctab[KF + k] (padded classes 0), cen;
+  // the statistics pass: the block's label counts and per-wave partial sums
+  const float* ctab = nullptr;
+  int* tcnt = nullptr;
+  float (*wsum)[2 * KF + 2] = nullptr;
+  float cen = 0.f;
+  if constexpr (LK == LK_DICE) {
+    __shared__ float ctab_s[2 * KF];
+    const float* cb = cw + (long)b * dice_coef_stride(K);
+    if (t < 2 * KF) ctab_s[t] = t % KF < K ? cb[(t / KF) * K + t % KF] : 0.f;
+    cen = cb[2 * K];
+    ctab = ctab_s;
+  }
+  if constexpr (LK == LK_DSTAT) {
+    __shared__ int tcnt_s[KF];
+    __shared__ float wsum_s[CT_NT / 64][2 * KF + 2];
+    if (t < KF) tcnt_s[t] = 0;
+    tcnt = tcnt_s;
+    wsum = wsum_s;
+  }
   __syncthreads();
   // pass 1: the run's two row-interpolated columns per class (registers, log2 units), the bound
   const float* la = lg + (min(max(ya - y0 + 1, 0), LH - 1)) * LW + c;
@@ -260,12 +300,85 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
   float inv[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) inv[j] = lv[j] >= 0 ? gs / sv[j] : 0.f;
+  if constexpr (LK == LK_DSTAT) {
+    // the statistics of the valid pixels this tile owns.  Per class: the run's P and I terms summed
+    // over the wave by the butterfly, the waves' sums met in LDS and added in wave order (no
+    // floating-point atomic anywhere: one fixed order); the label counts are integers
+    const bool rown = Y >= 4 * y0 && Y < 4 * (y0 + CT_Y);
+    float ow[4], ls = 0.f, lc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int X = X0 + j;
+      const bool own = lv[j] >= 0 && rown && X >= 4 * x0 && X < 4 * (x0 + CT_X);
+      ow[j] = own ? inv[j] : 0.f;
+      if (own) {
+        ls += target_nll(la, lb, lv[j] * LP, wa2, wb2, cl[j], cr[j], shv[j], sv[j]);
+        lc += 1.f;
+        atomicAdd(&tcnt[lv[j]], 1);
+      }
+    }
+    const int wv = t >> 6;
+    const bool lane0 = (t & 63) == 0;
+#pragma unroll
+    for (int k = 0; k < KF; ++k) {
+      float pk = 0.f, ik = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float p = ow[j] * __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -shv[j])));
+        pk += p;
+        ik += k == lv[j] ? p : 0.f;
+      }
+      pk = wave_sum(pk);
+      ik = wave_sum(ik);
+      if (lane0) {
+        wsum[wv][k] = ik;
+        wsum[wv][KF + k] = pk;
+      }
+    }
+    ls = wave_sum(ls);
+    lc = wave_sum(lc);
+    if (lane0) {
+      wsum[wv][2 * KF] = ls;
+      wsum[wv][2 * KF + 1] = lc;
+    }
+    __syncthreads();
+    float* pb = part + (long)blockIdx.x * dice_part_stride(K);
+    if (t < 2 * KF + 2) {
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < CT_NT / 64; ++i) a += wsum[i][t];
+      const int k = t % KF;
+      if (t >= 2 * KF) pb[3 * K + t - 2 * KF] = a;
+      else if (k < K) pb[(t / KF) * K + k] = a;
+    } else if (t >= 128 && t < 128 + K) {
+      pb[2 * K + t - 128] = (float)tcnt[t - 128];   // <= 768 pixels a tile: exact
+    }
+    return;
+  }
   // per pixel: pl = its loss, pn = its share of the normaliser, pc = the factor on (p - onehot)
   float pl[4], pn[4], pc[4], S[4];
   if constexpr (LK == LK_CE) {
     // pl is formed below, for the pixels the tile owns only (no other use of the target logit)
 #pragma unroll
     for (int j = 0; j < 4; ++j) pc[j] = gs;
+  } else if constexpr (LK == LK_DICE) {
+    // pass 2b: sum_k u_k p_k, u_k = c'_k - [k = y] a'_k (a padded class and an invalid pixel: p = 0)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) S[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < KF; ++k) {
+      const float ck = ctab[k], ak = ctab[KF + k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -shv[j])));
+        S[j] = __builtin_fmaf(e * inv[j], k == lv[j] ? ck - ak : ck, S[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      asm volatile("" : "+v"(S[j]));              // complete here, as kind 2's
+      pc[j] = cen;
+    }
   } else {
     // -log p_y of the valid pixels
     float nll[4];
@@ -319,7 +432,7 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
       }
     }
   }
-  if constexpr (FWD) {
+  if constexpr (FWD && LK != LK_DICE) {
     // loss of the valid pixels this tile owns (full-res [4 y0, 4 y0 + 4 CT_Y) x [4 x0, 4 x0 + 4 CT_X))
     float ls = 0.f, lc = 0.f;
     const bool rown = Y >= 4 * y0 && Y < 4 * (y0 + CT_Y);
@@ -350,7 +463,25 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
   float* trow = t1 + (act ? ri : 0) * CT_X * KP;
   float* wrow = (act && c < CT_X) ? trow + c * KP : t1 + CT_R * CT_X * KP;
   float sl[KF];
-  if constexpr (LK == LK_FOCAL) {
+  if constexpr (LK == LK_DICE) {
+    // as kind 2's pass 3 below, with u from the table: g = p (u - S + cen)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(shv[j]), "+v"(lv[j]));
+#pragma unroll
+    for (int k = 0; k < KF; ++k) {
+      const float ck = ctab[k], ak = ctab[KF + k];
+      float gl = 0.f, gr = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -shv[j])));
+        const float g = e * inv[j] * ((k == lv[j] ? ck - ak : ck) - S[j] + cen);
+        gl = __builtin_fmaf(cl[j], g, gl);
+        gr = __builtin_fmaf(cr[j], g, gr);
+      }
+      wrow[k] = gr;
+      sl[k] = gl;
+    }
+  } else if constexpr (LK == LK_FOCAL) {
     // the same exponentials and target selects as pass 2b, on purpose: opaque copies of the shifts
     // and classes keep the compiler from carrying pass 2b's per-class values (160 per thread and
     // kind) across to here instead (scratch)
@@ -409,7 +540,7 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
       if (lv[j] >= 0) trow[(c - 1) * KP + lv[j]] -= cl[j] * pc[j];
   }
   __syncthreads();
-  if constexpr (FWD) {
+  if constexpr (FWD && LK != LK_DICE) {
     if (t == 0) {
       float a = 0.f, n = 0.f;
 #pragma unroll

@@ -1810,6 +1810,44 @@ class UpsampleLossF(Function):
         return _scale_adjoint(ctx, adj, dloss, out), None, None, None, None, None
 
 
+class UpsampleDiceF(Function):
+    """F.interpolate(logits, (H, W), bilinear) + dice_scale * DiceLoss(smooth) + ce_scale *
+    CrossEntropyLoss (utils/loss_opr.py: DiceLoss is (0, 1), DiceCELoss(alpha) is (1 - alpha, alpha))
+    fused (cmx_upsample_dice_fwd_adj): a statistics pass and its finalize give the loss, then the
+    gradient pass writes the fp32 bilinear adjoint, final up to dloss; the backward scales it
+    (cmx_upsample_ce_bwd_scale).  spec = (ce_scale, dice_scale, smooth).  Without a backward to come the
+    gradient pass is not launched.  No materialised fallback: outside H = 4h, W = 4w, K <= 40 this
+    raises NotImplementedError."""
+
+    @staticmethod
+    def forward(ctx, logits, label, dims, ignore, spec):
+        B, h, w, H, W, Kc = dims
+        ce_scale, dice_scale, smooth = spec
+        logits = _c(logits)
+        f32 = dict(dtype=torch.float32, device=logits.device)
+        out = torch.empty(3, **f32)
+        stats = torch.empty(B, Kc, 3, **f32)
+        adj = torch.empty(B, h * w, Kc, **f32) if ctx.needs_input_grad[0] else None
+        ws = K._ws(K.query("cmx_upsample_dice_workspace", B, h, w, Kc), logits.device)
+        st = K._lib.try_call("cmx_upsample_dice_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(adj), K.ptr(out),
+                             K.ptr(stats), K.ptr(ws), B, h, w, H, W, Kc, ignore, float(ce_scale), float(dice_scale),
+                             float(smooth), K.dtype_code(logits), K.stream())
+        if st == K._lib.CMX_ERR_SHAPE:
+            raise NotImplementedError(f"fused upsample + Dice loss: {K._lib.last_error()}; only CrossEntropyLoss has "
+                                      "a materialised path for other shapes")
+        if st != 0:
+            raise K._lib.CMXError(f"cmx_upsample_dice_fwd_adj failed ({st}): {K._lib.last_error()}")
+        ctx.save_for_backward(adj, out)
+        ctx.ldtype, ctx.lshape = logits.dtype, logits.shape
+        return out[0]             # a view of the kernel's result (no copy launch)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        adj, out = ctx.saved_tensors
+        dloss = _c(dloss.reshape(1).to(torch.float32))
+        return _scale_adjoint(ctx, adj, dloss, out), None, None, None, None
+
+
 def upsample_logits_nchw(logits, B, h, w, H, W, Kc):
     out = torch.empty(B, Kc, H, W, dtype=torch.float32, device=logits.device)
     K.call("cmx_bilinear_fwd_nchw_f32", K.ptr(_c(logits)), K.ptr(out), B, h, w, H, W, Kc, K.dtype_code(logits),

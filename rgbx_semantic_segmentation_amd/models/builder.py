@@ -73,15 +73,23 @@ def backward_segment(name: str) -> int:
 DECODERS = {"MLPDecoder": MLPDecoder.DecoderHead, "MLPDecoderpp": MLPDecoderpp.DecoderHead}
 
 SUPPORTED_CRITERIA = ("nn.CrossEntropyLoss(reduction='mean'[, weight=w]), FocalLoss(reduction='mean', gamma == 0 or "
-                      "gamma >= 1), FocalLoss2d(reduction='mean'[, weight=w]) and CE_Focal = the tuple "
+                      "gamma >= 1), FocalLoss2d(reduction='mean'[, weight=w]), DiceLoss(reduction='mean'), "
+                      "DiceCELoss(reduction='mean') and CE_Focal = the tuple "
                       "(nn.CrossEntropyLoss(reduction='mean'), FocalLoss(...))")
+
+
+class DiceSpec(tuple):
+    """UpsampleDiceF's (ce_scale, dice_scale, smooth): a type of its own, so that forward tells it
+    from UpsampleLossF's 5-tuple."""
+    __slots__ = ()
 
 
 def _loss_plan(criterion):
     """(ignore_index, spec, class weight) of a supported criterion (train.py:70-88), else
     NotImplementedError naming the supported set.  spec None: plain CrossEntropyLoss, the
-    UpsampleCEF path; otherwise UpsampleLossF's (kind, gamma, alpha, ce_scale, focal_scale)."""
-    from ..utils.loss_opr import CE_FOCAL_WEIGHT, FocalLoss, FocalLoss2d, check_focal_gamma
+    UpsampleCEF path; a DiceSpec: DiceLoss / DiceCELoss, the UpsampleDiceF path; otherwise
+    UpsampleLossF's (kind, gamma, alpha, ce_scale, focal_scale)."""
+    from ..utils.loss_opr import CE_FOCAL_WEIGHT, DiceCELoss, DiceLoss, FocalLoss, FocalLoss2d, check_focal_gamma
 
     def refuse(why):
         raise NotImplementedError(f"criterion: {why}; on the hot path: {SUPPORTED_CRITERIA}")
@@ -111,6 +119,24 @@ def _loss_plan(criterion):
         if criterion.loss.reduction != "mean":
             refuse(f"FocalLoss2d(reduction={criterion.loss.reduction!r})")
         return int(criterion.loss.ignore_index), (F.LOSS_FOCAL2D, 0.0, 0.0, 1.0, 0.0), criterion.loss.weight
+    def dice(c):
+        if c.reduction != "mean":
+            refuse(f"DiceLoss(reduction={c.reduction!r})")
+        if not float(c.smooth) > 0:
+            refuse(f"DiceLoss(smooth={c.smooth!r})")
+        return float(c.smooth)
+
+    if isinstance(criterion, DiceLoss):
+        return int(criterion.ignore_index), DiceSpec((0.0, 1.0, dice(criterion))), None
+    if isinstance(criterion, DiceCELoss):
+        smooth, alpha = dice(criterion.dice), float(criterion.alpha)
+        if not plain_ce(criterion.ce) or criterion.ce.weight is not None:
+            refuse("DiceCELoss whose ce is not an unweighted CrossEntropyLoss")
+        if int(criterion.ce.ignore_index) != int(criterion.dice.ignore_index):
+            refuse("DiceCELoss whose two terms ignore different labels")
+        if not 0.0 <= alpha <= 1.0:
+            refuse(f"DiceCELoss(alpha={criterion.alpha!r})")
+        return int(criterion.ce.ignore_index), DiceSpec((1.0 - alpha, alpha, smooth)), None
     if isinstance(criterion, (tuple, list)) and len(criterion) == 2 and isinstance(criterion[1], FocalLoss) \
             and plain_ce(criterion[0]):
         ce, fl = criterion
@@ -317,4 +343,6 @@ class EncoderDecoder(nn.Module):
         dims = (B, h, w, H, W, self.num_classes)
         if self._loss_spec is None:        # plain CrossEntropyLoss
             return F.UpsampleCEF.apply(logits, label, dims, self.ignore_index)
+        if isinstance(self._loss_spec, DiceSpec):
+            return F.UpsampleDiceF.apply(logits, label, dims, self.ignore_index, self._loss_spec)
         return F.UpsampleLossF.apply(logits, label, dims, self.ignore_index, self._loss_spec, self._loss_weight)

@@ -4,10 +4,11 @@ signatures at the reference's import path.
 
 On the training hot path ``EncoderDecoder`` never calls these modules' ``forward``: it reads
 their hyper-parameters and runs ``cmx_upsample_loss_fwd_adj`` on the low-resolution logits
-(functions.UpsampleLossF).  ``forward(pred, target)`` is the plain-PyTorch statement of the same
+(functions.UpsampleLossF; DiceLoss / DiceCELoss: ``cmx_upsample_dice_fwd_adj``,
+functions.UpsampleDiceF).  ``forward(pred, target)`` is the plain-PyTorch statement of the same
 math on full-resolution logits (B, K, H, W): API compatibility off the hot path, and the tests'
-fp64 reference.  ``focal_grad`` / ``focal2d_grad`` are the closed-form per-pixel gradients the
-kernels implement.
+fp64 reference.  ``focal_grad`` / ``focal2d_grad`` / ``dice_grad`` are the closed-form gradients
+the kernels implement.
 """
 from __future__ import annotations
 
@@ -77,7 +78,70 @@ class FocalLoss2d(nn.Module):
         return self.loss((1 - F.softmax(input, 1)) ** 2 * F.log_softmax(input, 1), target)
 
 
+def _dice_terms(pred, target, ignore_index):
+    """(p masked, onehot masked) (B, K, H, W) in pred's dtype: the softmax and the one-hot of
+    clamp(target, 0, K - 1), both zeroed where target == ignore_index (FocalLoss's label rule)."""
+    K = pred.shape[1]
+    valid = (target != ignore_index).unsqueeze(1).to(pred.dtype)
+    onehot = F.one_hot(target.clamp(0, K - 1), K).movedim(-1, 1).to(pred.dtype)
+    return torch.softmax(pred, dim=1) * valid, onehot * valid
+
+
+class DiceLoss(nn.Module):
+    """1 - dice, dice[b, k] = (2 I + smooth) / (P + T + smooth) with, per image b and class k over
+    the valid pixels, I = sum p_k [y = k], P = sum p_k, T = sum [y = k]; 'mean' / 'sum' reduce
+    dice over (b, k), anything else returns 1 - dice (B, K).  Nothing valid: every dice is 1."""
+
+    def __init__(self, smooth=1e-6, ignore_index=255, reduction='mean'):
+        super().__init__()
+        self.smooth = smooth
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+
+    def forward(self, preds, targets):
+        p, onehot = _dice_terms(preds, targets, self.ignore_index)
+        inter = (p * onehot).sum(dim=(2, 3))
+        union = p.sum(dim=(2, 3)) + onehot.sum(dim=(2, 3))
+        dice = (2 * inter + self.smooth) / (union + self.smooth)
+        if self.reduction == 'mean':
+            return 1 - dice.mean()
+        if self.reduction == 'sum':
+            return 1 - dice.sum()
+        return 1 - dice
+
+
+class DiceCELoss(nn.Module):
+    """alpha * DiceLoss + (1 - alpha) * nn.CrossEntropyLoss, both with the same ignore_index and
+    reduction."""
+
+    def __init__(self, alpha=0.5, ignore_index=255, reduction='mean'):
+        super().__init__()
+        self.alpha = alpha
+        self.dice = DiceLoss(ignore_index=ignore_index, reduction=reduction)
+        self.ce = nn.CrossEntropyLoss(ignore_index=ignore_index, reduction=reduction)
+
+    def forward(self, preds, targets):
+        return self.alpha * self.dice(preds, targets) + (1 - self.alpha) * self.ce(preds, targets)
+
+
 # ------------------------------------------------------------------ closed-form gradients
+def dice_grad(z, target, ignore_index, smooth):
+    """d(DiceLoss, mean)/dz for logits z (B, K, H, W): with U = P + T,
+    u_k = v (c[b, k] - [y = k] a[b, k]), c = (2 I + s) / ((U + s)^2 B K), a = 2 / ((U + s) B K),
+    dl/dz_j = p_j (u_j - sum_k u_k p_k); zero at ignored pixels."""
+    B, K = z.shape[:2]
+    valid = (target != ignore_index).unsqueeze(1).to(z.dtype)
+    pm, onehot = _dice_terms(z, target, ignore_index)
+    inter = (pm * onehot).sum(dim=(2, 3))
+    union = pm.sum(dim=(2, 3)) + onehot.sum(dim=(2, 3))
+    c = ((2 * inter + smooth) / ((union + smooth) ** 2 * B * K))[:, :, None, None]
+    a = (2 / ((union + smooth) * B * K))[:, :, None, None]
+    u = c * valid - a * onehot
+    p = torch.softmax(z, dim=1)
+    return p * (u - (u * p).sum(1, keepdim=True))
+
+
+
 def focal_grad(z, target, ignore_label, gamma, alpha):
     """d(per-pixel FocalLoss)/dz for logits z (B, K, H, W), zero at invalid pixels (no 1/n):
     u_k = dl/dp_k, dl/dz_j = p_j (u_j - sum_k u_k p_k)."""

@@ -85,6 +85,62 @@ def loss():
     return res
 
 
+def dice():
+    """DiceCELoss(0.5) on the fused path (cmx_upsample_dice_fwd_adj) at the B2 shape (2, 120, 160, 40)
+    bf16: the loss-only pair (statistics pass + finalize, adj = NULL) and all three launches by HIP
+    events, each launch's own device time from a kernel trace of the same calls (torch.profiler), beside
+    two yardsticks in the same process: the existing one-pass forms (plain CE, focal gamma = 0) and
+    eager PyTorch DiceCELoss forward + backward on the materialised upsample."""
+    import torch.nn.functional as Fn
+    from torch.profiler import ProfilerActivity, profile
+    from rgbx_semantic_segmentation_amd.functions import LOSS_FOCAL
+    from rgbx_semantic_segmentation_amd.utils.loss_opr import DiceCELoss
+    B, h, w, Kc = 2, 120, 160, 40
+    H, W = 4 * h, 4 * w
+    logits = torch.randn(B, h * w, Kc, device="cuda").to(torch.bfloat16)
+    label = torch.randint(0, Kc, (B, H, W), device="cuda")
+    label[:, :20, :20] = 255
+    out, stats = torch.empty(3, device="cuda"), torch.empty(B, Kc, 3, device="cuda")
+    adj = torch.empty(B, h * w, Kc, device="cuda")
+    ws = K._ws(max(K.query("cmx_upsample_dice_workspace", B, h, w, Kc), K.query("cmx_upsample_loss_workspace", B, h, w),
+                   K.query("cmx_upsample_ce_workspace", B, H, W)), "cuda")
+    fused = lambda a: K.call("cmx_upsample_dice_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(a), K.ptr(out),
+                             K.ptr(stats), K.ptr(ws), B, h, w, H, W, Kc, 255, 0.5, 0.5, 1e-6, 1, K.stream())
+    res = {"dice loss only (stats + finalize)": timeit(lambda: fused(None)),
+           "dice training (3 launches)": timeit(lambda: fused(adj))}
+    for _ in range(3):
+        fused(adj)
+    torch.cuda.synchronize()
+    n = 20
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(n):
+            fused(adj)
+        torch.cuda.synchronize()
+    for ev in prof.key_averages():
+        t = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+        if ev.count == n and t > 0:
+            # loss_cells<bf16, LK_DSTAT = 4 / LK_DICE = 3, 0, true>, demangled or not
+            kind = ("finalize" if "dice_finalize" in ev.key
+                    else "statistics pass" if ("Li4ELi0" in ev.key or ", 4, 0," in ev.key)
+                    else "gradient pass" if ("Li3ELi0" in ev.key or ", 3, 0," in ev.key) else ev.key[:40])
+            res[f"  launch: {kind}"] = t / n
+    res["ce_fwd_adj (plain CE)"] = timeit(lambda: K.call(
+        "cmx_upsample_ce_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(adj), K.ptr(out), K.ptr(ws), B, h, w, H, W, Kc,
+        255, 1, K.stream()))
+    res["loss_fwd_adj focal_g0"] = timeit(lambda: K.call(
+        "cmx_upsample_loss_fwd_adj", K.ptr(logits), K.ptr(label), 0, K.ptr(adj), K.ptr(out), K.ptr(ws), B, h, w, H, W,
+        Kc, 255, LOSS_FOCAL, 0.0, 0.25, 0.0, 1.0, 1, K.stream()))
+    eager = DiceCELoss(alpha=0.5, ignore_index=255).cuda()
+    x = logits.view(B, h, w, Kc).permute(0, 3, 1, 2).float().requires_grad_(True)
+
+    def step():
+        x.grad = None
+        up = Fn.interpolate(x, size=(H, W), mode="bilinear", align_corners=False)
+        eager(up, label).backward()
+    res["eager fwd+bwd DiceCELoss"] = timeit(step, iters=10)
+    return res
+
+
 def decoder():
     """The decoder fold's full-resolution passes at the B2 shapes: the upsample-sum (up3) + the c1
     residual GEMM against the c1 GEMM with the upsample in its epilogue, and the 3-grid adjoint

@@ -60,6 +60,9 @@ def build_parser():
     p.add_argument("--fl-alpha", type=float, default=0.25, help="config.FL_alpha (config.py:65)")
     p.add_argument("--class-weights", default="",
                    help="comma-separated class weights (num-classes floats) for CrossEntropyLoss / FocalLoss2d")
+    p.add_argument("--dice-alpha", type=float, default=None,
+                   help="with --criterion CrossEntropyLoss: DiceCELoss(alpha=A) = A * DiceLoss + (1 - A) * CE "
+                        "for 0 < A < 1, DiceLoss for A = 1")
     p.add_argument("--optimizer", default="AdamW",
                    help="config.optimizer (train.py:114-135): " + ", ".join(OPTIMIZERS))
     p.add_argument("--momentum", type=float, default=0.9, help="config.momentum (config.py:70), SGDM only")
@@ -84,9 +87,22 @@ def build_parser():
 def build_criterion(args, background=255):
     """The criterion object(s) train.py:70-88 builds for config.criterion; other names raise."""
     from torch import nn
-    from rgbx_semantic_segmentation_amd.utils.loss_opr import FocalLoss, FocalLoss2d
+    from rgbx_semantic_segmentation_amd.utils.loss_opr import DiceCELoss, DiceLoss, FocalLoss, FocalLoss2d
     if args.criterion not in CRITERIA:
-        raise NotImplementedError(f"criterion {args.criterion} (on the HIP path: {', '.join(CRITERIA)})")
+        raise NotImplementedError(f"criterion {args.criterion} (on the HIP path: {', '.join(CRITERIA)}; "
+                                  "DiceCELoss / DiceLoss: --criterion CrossEntropyLoss --dice-alpha A)")
+    if args.dice_alpha is not None:
+        # DiceCELoss by flag: the name itself stays refused above
+        if args.criterion != "CrossEntropyLoss":
+            raise NotImplementedError(f"--dice-alpha with --criterion {args.criterion}: DiceCELoss combines Dice "
+                                      "with CrossEntropyLoss only")
+        if args.class_weights:
+            raise NotImplementedError("--dice-alpha with --class-weights: DiceCELoss takes no class weight")
+        if not 0.0 < args.dice_alpha <= 1.0:
+            raise ValueError(f"--dice-alpha {args.dice_alpha}: 0 < A <= 1")
+        if args.dice_alpha == 1.0:
+            return DiceLoss(ignore_index=background, reduction="mean")
+        return DiceCELoss(alpha=args.dice_alpha, ignore_index=background, reduction="mean")
     weight = None
     if args.class_weights:
         weight = [float(v) for v in args.class_weights.split(",")]
