@@ -348,7 +348,9 @@ int cmx_reduce_grouped(const void* recs, int nrec, int total_blocks, hipStream_t
 
 /* ---- fused AdamW over the flat parameter buffer (train.py:128-129, init_func.py:33-57). */
 /* tickets (all three steps): cmx_adamw_tickets() zeroed uint32s owned by the optimizer (the step count's
- * arrival counters; each launch leaves them zero); NULL = the library's device-global set */
+ * arrival counters; each launch leaves them zero); NULL = the library's device-global set.
+ * Refusals precede the launch (all three steps): CMX_ERR_ARG for a NULL p, g, m, v, decay64, lr_ptr or step_ptr,
+ * CMX_ERR_SHAPE for n % 64, CMX_ERR_DTYPE for a shadow whose dtype is neither 1 (bf16) nor 2 (f16). */
 size_t cmx_adamw_tickets(void);
 int cmx_adamw_step(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, const uint8_t* decay64, int64_t n, const float* lr_ptr, float* step_ptr, double beta1, double beta2, float eps, double weight_decay, float grad_scale, unsigned* tickets, hipStream_t stream);
 /* ---- dynamic loss scaling: torch.cuda.amp.GradScaler of the reference's AMP path (train.py:13,56,185-198, config 5).

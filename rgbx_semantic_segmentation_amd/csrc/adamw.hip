@@ -24,8 +24,8 @@
 
 // step-count tickets: a block takes a ticket of its group of ADAMW_GRP consecutive blocks; the
 // last of a group takes one of the top-level ticket; the last of those stores t.  One counter
-// for 65 K blocks serialised 65 K atomics on one address (770 us per launch); spread over 1024
-// group counters they overlap (no more than 64 arrivals per address).
+// for 65 K blocks serialised 65 K atomics on one address (770 us per launch); spread over the
+// ADAMW_NGRP = 4096 group counters they overlap (no more than 64 arrivals per address).
 constexpr int ADAMW_GRP = 64;
 constexpr int ADAMW_NGRP = 4096;
 __device__ unsigned int g_adamw_ticket = 0;
@@ -217,6 +217,8 @@ static int adamw_launch(float* p, const float* g, float* m, float* v, void* shad
                         const uint8_t* decay64, int64_t n, const float* lr_ptr, float* step_ptr, double beta1,
                         double beta2, float eps, double weight_decay, float grad_scale, const float* loss_scale,
                         const float* found_inf, int store_step, int max_blocks, unsigned* tickets, hipStream_t s) {
+  CMX_REQUIRE(p && g && m && v && decay64 && lr_ptr && step_ptr, CMX_ERR_ARG,
+              "adamw: p, g, m, v, decay64, lr_ptr and step_ptr must not be NULL");
   CMX_REQUIRE(n % 64 == 0, CMX_ERR_SHAPE, "adamw: n must be a multiple of 64");
   CMX_REQUIRE(!shadow || shadow_dtype == 1 || shadow_dtype == 2, CMX_ERR_DTYPE, "adamw: shadow dtype %d", shadow_dtype);
   // CMX_ADAMW_BLOCKS caps the grid (A/B knob; each block takes one relaxed ticket, so the
