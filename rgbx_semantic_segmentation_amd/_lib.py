@@ -3,6 +3,14 @@
 The argument/return types are derived by parsing ``include/cmx_hip.h`` (shipped inside
 the package as ``cmx_hip.h``), so the header is the single source of truth for the ABI.
 
+``call`` / ``try_call`` / ``query`` / ``refusable`` take an entry point's name and its arguments in
+header order; ``marshal`` converts them by the kind the header declares for each parameter:
+ * pointer (any ``*`` but ``const char*``): a ``torch.Tensor`` (its ``data_ptr()``: a view passes its
+   own address, nothing is copied), ``None`` (NULL) or an integer address, passed through unchanged;
+ * stream (``hipStream_t``, always last): an integer handle; left out, ``stream()`` is appended;
+ * scalar (the rest): a Python number (``bool`` becomes ``int``) or ``bytes``, never a tensor.
+Any other argument count is a ``TypeError`` (ctypes alone accepts surplus arguments silently).
+
 The library is loaded AFTER ``import torch`` so that its ``libamdhip64.so.7`` dependency
 resolves (by SONAME) to the HIP runtime torch already loaded: kernels then run on torch's
 streams and are captured by torch's HIP graphs.  There is no fallback: if the library is
@@ -44,30 +52,42 @@ def _ctype(decl: str):
             "size_t": ctypes.c_size_t, "double": ctypes.c_double, "hipStream_t": ctypes.c_void_p, "void": None}[base]
 
 
+POINTER, STREAM, SCALAR = "pointer", "stream", "scalar"
+
+
+def _kind(decl: str) -> str:
+    if "*" in decl:
+        return SCALAR if decl.strip().startswith("const char") else POINTER     # a C string: bytes
+    return STREAM if "hipStream_t" in decl.split() else SCALAR
+
+
+class Signature(tuple):
+    """(restype, [argtypes]) of one declaration; ``kinds`` holds POINTER / STREAM / SCALAR per parameter."""
+    kinds: tuple = ()
+
+
+def _header(path: str | None) -> str:
+    return open(path or next(p for p in HEADER_PATHS if os.path.exists(p))).read()
+
+
 def parse_header(path: str | None = None):
-    """Return {name: (restype, [argtypes])} for every declaration in cmx_hip.h."""
-    if path is None:
-        path = next(p for p in HEADER_PATHS if os.path.exists(p))
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    """Return {name: Signature (restype, [argtypes]), .kinds} for every declaration in cmx_hip.h."""
+    text = re.sub(r"/\*.*?\*/", "", _header(path), flags=re.S)
     out = {}
     for m in re.finditer(r"^\s*([A-Za-z_][\w\s\*]*?)\b(cmx_\w+)\s*\(([^)]*)\)\s*;", text, re.M):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
-        rt = _ctype(ret.strip() + " r") if "*" not in ret else _ctype(ret.strip() + " r")
-        if ret.strip() == "const char*":
-            rt = ctypes.c_char_p
-        argt = [] if args in ("", "void") else [_ctype(a) for a in args.split(",")]
-        out[name] = (rt, argt)
+        rt = ctypes.c_char_p if ret.strip() == "const char*" else _ctype(ret.strip() + " r")
+        decls = [] if args in ("", "void") else args.split(",")
+        out[name] = Signature((rt, [_ctype(a) for a in decls]))
+        out[name].kinds = tuple(_kind(a) for a in decls)
     return out
 
 
 def header_abi_version(path: str | None = None) -> int:
     """The CMX_ABI_VERSION the header defines (the revision the bindings below are parsed from)."""
-    if path is None:
-        path = next(p for p in HEADER_PATHS if os.path.exists(p))
-    m = re.search(r"^#define\s+CMX_ABI_VERSION\s+(\d+)", open(path).read(), re.M)
+    m = re.search(r"^#define\s+CMX_ABI_VERSION\s+(\d+)", _header(path), re.M)
     if m is None:
-        raise CMXError(f"{path} defines no CMX_ABI_VERSION")
+        raise CMXError(f"{path or 'cmx_hip.h'} defines no CMX_ABI_VERSION")
     return int(m.group(1))
 
 
@@ -87,6 +107,7 @@ def _load():
         fn = getattr(lib, name)
         fn.argtypes = argt
         fn.restype = rt
+        assert STREAM not in sigs[name].kinds[:-1], f"{name}: hipStream_t must be the last parameter"
     return lib, sigs
 
 
@@ -97,35 +118,6 @@ def last_error() -> str:
     return LIB.cmx_last_error().decode()
 
 
-# measurement hook (roofline.measure_gemm_family): observer(name, fn, args) runs right after a
-# successful call, while the caller still holds every buffer the arguments point to
-observer = None
-
-
-def call(name: str, *args) -> None:
-    """Invoke an int-returning entry point; raise CMXError on a negative status."""
-    fn = getattr(LIB, name)
-    st = fn(*args)
-    if st != 0:
-        raise CMXError(f"{name} failed ({st}): {last_error()}")
-    if observer is not None:
-        observer(name, fn, args)
-
-
-def try_call(name: str, *args) -> int:
-    """Invoke an int-returning entry point and return its status (the caller decides what a
-    refusal means); the measurement observer sees it only when it succeeded."""
-    fn = getattr(LIB, name)
-    st = int(fn(*args))
-    if st == 0 and observer is not None:
-        observer(name, fn, args)
-    return st
-
-
-def query(name: str, *args) -> int:
-    return int(getattr(LIB, name)(*args))
-
-
 def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -134,11 +126,75 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def _pointer_arg(a):
+    return a.data_ptr() if isinstance(a, torch.Tensor) else a
+
+
+def _scalar_arg(a):
+    if isinstance(a, torch.Tensor):
+        raise TypeError("a tensor was passed where the header declares a scalar")
+    return int(a) if a is True or a is False else a
+
+
+# per entry point, built once: (the C function, one converter per parameter, takes a trailing stream)
+_BOUND = {name: (getattr(LIB, name), tuple(_pointer_arg if k == POINTER else _scalar_arg for k in sig.kinds),
+                 sig.kinds[-1:] == (STREAM,)) for name, sig in SIGNATURES.items()}
+
+
+def marshal(name: str, args: tuple) -> tuple:
+    """The argument tuple ctypes is given for ``args`` of entry point ``name`` (module docstring)."""
+    _, convs, takes_stream = _BOUND[name]
+    if len(args) != len(convs):
+        if not (takes_stream and len(args) == len(convs) - 1):
+            raise TypeError(f"{name} takes {len(convs)} arguments, {len(args)} given")
+        args = (*args, stream())
+    return tuple([c(a) for c, a in zip(convs, args)])
+
+
+# measurement hook (roofline.measure_gemm_family): observer(name, fn, args) runs right after a
+# successful call with the marshalled arguments (fn(*args) repeats the launch), while the caller
+# still holds every buffer they point to
+observer = None
+
+
+def try_call(name: str, *args) -> int:
+    """Invoke an int-returning entry point and return its status (the caller decides what a
+    refusal means); the measurement observer sees it only when it succeeded."""
+    fn = _BOUND[name][0]
+    args = marshal(name, args)
+    st = int(fn(*args))
+    if st == 0 and observer is not None:
+        observer(name, fn, args)
+    return st
+
+
+def call(name: str, *args) -> None:
+    """Invoke an int-returning entry point; raise CMXError on a negative status."""
+    refusable(name, (), *args)
+
+
+REFUSED = object()
+
+
+def refusable(name: str, refusals: tuple, *args):
+    """``call``, except that a status among ``refusals`` (the entry point declines this problem:
+    CMX_ERR_ARG / CMX_ERR_SHAPE) returns REFUSED for the caller to take another path."""
+    st = try_call(name, *args)
+    if st in refusals:
+        return REFUSED
+    if st != 0:
+        raise CMXError(f"{name} failed ({st}): {last_error()}")
+
+
+def query(name: str, *args) -> int:
+    return int(_BOUND[name][0](*marshal(name, args)))
+
+
+# the dtype codes of the C-ABI (cmx_dtype)
+DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
 def dtype_code(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
-        return 0
-    if t.dtype == torch.bfloat16:
-        return 1
-    if t.dtype == torch.float16:
-        return 2
-    raise CMXError(f"unsupported dtype {t.dtype}")
+    if t.dtype not in DTYPE_CODES:
+        raise CMXError(f"unsupported dtype {t.dtype}")
+    return DTYPE_CODES[t.dtype]

@@ -79,19 +79,17 @@ class TrainPre:
                              f"{tuple(gt.shape)} HxW of the same size")
         h, w = rgb.shape[:2]
         sh, sw = prm["sh"], prm["sw"]
-        st = L.stream()
         m = int(bool(prm["mirror"]))
         rs = torch.empty(sh, sw, 3, dtype=torch.uint8, device=dev)
         xs = torch.empty_like(rs)
         gs = torch.empty(sh, sw, dtype=torch.uint8, device=dev)
-        L.call("cmx_aug_resize_u8", L.ptr(rgb), h, w, 3, L.ptr(rs), sh, sw, 0, m, -1, st)
-        L.call("cmx_aug_resize_u8", L.ptr(x), h, w, 3, L.ptr(xs), sh, sw, 0, m, -1, st)
-        L.call("cmx_aug_resize_u8", L.ptr(gt), h, w, 1, L.ptr(gs), sh, sw, 1, m, self.num_classes - 1, st)
-        L.call("cmx_aug_color_jitter_u8", L.ptr(rs), sh, sw, float(prm["bf"]), float(prm["sf"]),
-               float(prm["hf"] * 180), st)
+        L.call("cmx_aug_resize_u8", rgb, h, w, 3, rs, sh, sw, 0, m, -1)
+        L.call("cmx_aug_resize_u8", x, h, w, 3, xs, sh, sw, 0, m, -1)
+        L.call("cmx_aug_resize_u8", gt, h, w, 1, gs, sh, sw, 1, m, self.num_classes - 1)
+        L.call("cmx_aug_color_jitter_u8", rs, sh, sw, float(prm["bf"]), float(prm["sf"]), float(prm["hf"] * 180))
         if prm["blur"]:
             rb = torch.empty_like(rs)
-            L.call("cmx_aug_blur5_u8", L.ptr(rs), L.ptr(rb), sh, sw, 3, st)
+            L.call("cmx_aug_blur5_u8", rs, rb, sh, sw, 3)
             rs = rb
         if out is None:
             out = (torch.empty(3, self.H, self.W, dtype=torch.float32, device=dev),
@@ -101,8 +99,8 @@ class TrainPre:
         assert ro.is_contiguous() and go.is_contiguous() and xo.is_contiguous()
         bx1, by1, bx2, by2 = prm["box"] if prm["box"] is not None else (0, 0, 0, 0)
         mn, sd = self.norm_mean, self.norm_std
-        L.call("cmx_aug_finalize", L.ptr(rs), L.ptr(xs), L.ptr(gs), sh, sw, self.H, self.W, bx1, by1, bx2, by2,
-               self.background, mn[0], mn[1], mn[2], sd[0], sd[1], sd[2], L.ptr(ro), L.ptr(xo), L.ptr(go), st)
+        L.call("cmx_aug_finalize", rs, xs, gs, sh, sw, self.H, self.W, bx1, by1, bx2, by2, self.background, *mn[:3],
+               *sd[:3], ro, xo, go)
         return out
 
     def __call__(self, rgb, gt, modal_x, out=None):
@@ -182,7 +180,7 @@ class TrainPre:
         stage.copy_(pin[:src_off + table_bytes], non_blocking=True)
         self._events[self._turn].record(st)
         mn, sd = self.norm_mean, self.norm_std
-        L.call("cmx_aug_batch", sbase + src_off, B, max_sh, max_sw, self.H, self.W, self.num_classes - 1,
+        L.call("cmx_aug_batch", stage[src_off:], B, max_sh, max_sw, self.H, self.W, self.num_classes - 1,
                self.background, mn[0], mn[1], mn[2], sd[0], sd[1], sd[2], st.cuda_stream)
         return out
 

@@ -34,7 +34,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import LIB, call, query, ptr, stream
+from ._lib import call, query
+from .kernels import _operand
 
 ENABLED = os.environ.get("CMX_DEFER", "1") == "1"
 
@@ -79,24 +80,13 @@ def arm() -> None:
         torch.autograd.Variable._execution_engine.queue_callback(flush)
 
 
-_H16 = {torch.bfloat16: 1, torch.float16: 2}
-
-
 def _h16_code(*ts) -> int:
     """1 (bf16) / 2 (fp16) when every operand has that 16-bit dtype and matches the queue's
     GEMMs, else 0 (not eligible: the caller runs the problem now)."""
-    code = _H16.get(ts[0].dtype, 0)
+    code = _lib.DTYPE_CODES.get(ts[0].dtype, 0)
     if code == 0 or any(t.dtype != ts[0].dtype for t in ts) or (_q.dtype and _q.dtype != code):
         return 0
     return code
-
-
-def _operand(t: torch.Tensor):
-    if t.stride(2) == 1:
-        return 0, t.stride(1), t.stride(0)
-    if t.stride(1) == 1:
-        return 1, t.stride(2), t.stride(0)
-    return None
 
 
 def wgrad(dz: torch.Tensor, x: torch.Tensor, Wg: torch.Tensor, bg: torch.Tensor | None = None) -> bool:
@@ -125,10 +115,8 @@ def wgrad(dz: torch.Tensor, x: torch.Tensor, Wg: torch.Tensor, bg: torch.Tensor 
     args = (A, B, Wg, bg, G, N, Nk, M, oa[1], ob[1], Wg.stride(1), oa[2], ob[2], Wg.stride(0), sdb)
     # validate now (shape / alignment / 31-bit extents) so a refusal falls back immediately
     rec = (ctypes.c_uint8 * _GREC)()
-    st = LIB.cmx_gemm_group_pack(ctypes.addressof(rec), ptr(A), ptr(B), ptr(Wg), ptr(bg), 1, G, N, Nk, M,
-                                 oa[1], ob[1], Wg.stride(1), oa[2], ob[2], Wg.stride(0), sdb, 1, 1, 1,
-                                 int(bg is not None), 1, 0)
-    if st <= 0:
+    if query("cmx_gemm_group_pack", ctypes.addressof(rec), A, B, Wg, bg, 1, G, N, Nk, M, oa[1], ob[1], Wg.stride(1),
+             oa[2], ob[2], Wg.stride(0), sdb, 1, 1, 1, bg is not None, 1, 0) <= 0:
         return False
     _q.gemms.append(args)
     _q.dtype = code
@@ -186,8 +174,7 @@ def reduce(src: torch.Tensor, dst: torch.Tensor, dst2: torch.Tensor | None, G: i
     """Queue dst/dst2 (+)= sum over nblk partial rows of src (see cmx_reduce_pack)."""
     if not _free:
         reserve()
-    _q.reds.append((src.data_ptr(), dst.data_ptr(), ptr(dst2), G, nblk, sg, sb, rows, cols, csplit, dg, ldd, dg2,
-                    ldd2, int(accumulate)))
+    _q.reds.append((src, dst, dst2, G, nblk, sg, sb, rows, cols, csplit, dg, ldd, dg2, ldd2, accumulate))
     _q.keep.append(src)
     _note_stream()
     arm()
@@ -234,7 +221,7 @@ def _table(nbytes: int) -> torch.Tensor:
 
 def _upload(table: torch.Tensor, nbytes: int, device) -> torch.Tensor:
     dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    call("cmx_upload", dev.data_ptr(), table.data_ptr(), nbytes, stream())
+    call("cmx_upload", dev, table, nbytes)
     if torch.cuda.is_current_stream_capturing():
         _graph_tables.append(table)          # every replay re-reads it
     else:
@@ -276,7 +263,7 @@ def _issue(max_blocks: int = 0) -> None:
         for c in convs:
             G, NIg, H, W, C, KH, KW, st, pad, Ho, Wo, N = c[4:16]
             dims.append((G, N, C + (1 if c[3] is not None else 0), NIg * Ho * Wo, c[3] is not None))
-        splits = [query("cmx_gemm_grouped_splitk", G, M, N, K, int(hb)) for (G, M, N, K, hb) in dims]
+        splits = [query("cmx_gemm_grouped_splitk", G, M, N, K, hb) for (G, M, N, K, hb) in dims]
         sizes = [query("cmx_gemm_workspace", G, M, N, s) if s > 1 else 0 for (G, M, N, K, hb), s in zip(dims, splits)]
         arena = torch.empty(max(1, sum((z + 255) // 256 * 64 for z in sizes)), dtype=torch.float32, device=device)
         nrec = len(dims)
@@ -289,29 +276,28 @@ def _issue(max_blocks: int = 0) -> None:
         blk, off = 0, 0
         for i in range(nrec):
             s, sz = splits[i], sizes[i]
-            ws = arena.data_ptr() + off if s > 1 else 0
+            ws = arena[off // 4:] if s > 1 else None
             if i < len(gemms):
                 A, B, Wg, bg, G, M, N, K, lda, ldb, ldc, sA, sB, sC, sdb = gemms[i]
-                nb = LIB.cmx_gemm_group_pack(base + i * _GREC, ptr(A), ptr(B), ptr(Wg), ptr(bg), ws, G, M, N, K, lda,
-                                             ldb, ldc, sA, sB, sC, sdb, 1, 1, 1, int(bg is not None), s, blk)
-                dst = Wg.data_ptr()
+                nb = query("cmx_gemm_group_pack", base + i * _GREC, A, B, Wg, bg, ws, G, M, N, K, lda, ldb, ldc, sA, sB,
+                           sC, sdb, 1, 1, 1, bg is not None, s, blk)
+                dst = Wg
             else:
                 (dy, x, Wg, bg, G, NIg, H, W, C, KH, KW, st, pad, Ho, Wo, Nout, tap, sdy, sx, sC, sdb) = \
                     convs[i - len(gemms)]
-                nb = LIB.cmx_gemm_group_pack_conv_wgrad(base + i * _GREC, ptr(dy), ptr(x), ptr(Wg), ptr(bg), ws, G, NIg,
-                                                        H, W, C, KH, KW, st, pad, Ho, Wo, Nout, tap, sdy, sx, sC, sdb, s,
-                                                        blk)
+                nb = query("cmx_gemm_group_pack_conv_wgrad", base + i * _GREC, dy, x, Wg, bg, ws, G, NIg, H, W, C, KH,
+                           KW, st, pad, Ho, Wo, Nout, tap, sdy, sx, sC, sdb, s, blk)
                 M, N, ldc = Nout, C + (1 if bg is not None else 0), KH * KW * C
-                dst = Wg.data_ptr() + 4 * tap * C
+                dst = Wg[..., tap * C:]
             if nb <= 0:
                 raise _lib.CMXError(f"grouped-GEMM record pack failed ({nb}): {_lib.last_error()}")
             blk += nb
             if s > 1:
                 # slabs: (G, s, M, Nr) fp32, Nr = real columns; then the bias-gradient column (G, s, M)
                 Nr = N - 1 if bg is not None else N
-                reds.append((ws, dst, 0, G, s, s * M * Nr, M * Nr, M, Nr, Nr, sC, ldc, 0, 0, 0))
+                reds.append((ws, dst, None, G, s, s * M * Nr, M * Nr, M, Nr, Nr, sC, ldc, 0, 0, 0))
                 if bg is not None:
-                    reds.append((ws + 4 * G * s * M * Nr, bg.data_ptr(), 0, G, s, s * M, M, 1, M, M, sdb, M, 0, 0, 0))
+                    reds.append((ws[G * s * M * Nr:], bg, None, G, s, s * M, M, 1, M, M, sdb, M, 0, 0, 0))
                 off += (sz + 255) // 256 * 256
         gtab = (table, gbytes, nrec, blk, dims, arena)
     if reds:
@@ -322,7 +308,7 @@ def _issue(max_blocks: int = 0) -> None:
         base = table.data_ptr() + gbytes
         rblk = 0
         for i, r in enumerate(reds):
-            nb = LIB.cmx_reduce_pack(base + i * _RREC, *r, rblk)
+            nb = query("cmx_reduce_pack", base + i * _RREC, *r, rblk)
             if nb <= 0:
                 raise _lib.CMXError(f"cmx_reduce_pack failed ({nb}): {_lib.last_error()}")
             rblk += nb
@@ -331,14 +317,14 @@ def _issue(max_blocks: int = 0) -> None:
         dev = _upload(table, total, device)
         if gtab is not None:
             _, _, nrec, blk, dims, arena = gtab
-            call("cmx_gemm_grouped_capped", dev.data_ptr(), nrec, blk, int(max_blocks) // 8 * 8, dcode, stream())
+            call("cmx_gemm_grouped_capped", dev, nrec, blk, int(max_blocks) // 8 * 8, dcode)
             keep.append(arena)
             if observer is not None:
                 # algorithmic work per problem: (G, M, real N, K) and operand / result bytes
                 work = [(G, M, N - (1 if hb else 0), K) for (G, M, N, K, hb) in dims]
                 observer(dev, nrec, blk, work, keep, dcode)
         if reds:
-            call("cmx_reduce_grouped", dev.data_ptr() + gbytes, len(reds), rblk, stream())
+            call("cmx_reduce_grouped", dev[gbytes:], len(reds), rblk)
     # the caching allocator may hand the queued buffers out again once this stream has
     # passed the launches above (stream-ordered reuse): dropping `keep` here is safe
     del keep

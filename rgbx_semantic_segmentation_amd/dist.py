@@ -144,12 +144,12 @@ class BucketedGradSync:
         out = torch.empty(P * shard, dtype=torch.bfloat16, device=t.device)
         if t.is_cuda:
             from . import _lib
-            _lib.call("cmx_cast_f32_bf16", _lib.ptr(mine), _lib.ptr(mine16), shard, _lib.stream())
+            _lib.call("cmx_cast_f32_bf16", mine, mine16, shard)
         else:
             mine16.copy_(mine)
         dist.all_gather_into_tensor(out, mine16, group=self.group)
         if t.is_cuda and n % 8 == 0:
-            _lib.call("cmx_cast_bf16_f32", _lib.ptr(out), _lib.ptr(t), n, _lib.stream())
+            _lib.call("cmx_cast_bf16_f32", out, t, n)
         else:
             t.copy_(out[:n])
 

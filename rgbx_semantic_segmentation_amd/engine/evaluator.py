@@ -52,7 +52,7 @@ def _resize_chw(x: torch.Tensor, oh: int, ow: int, as_uint8: bool = False) -> to
         return x
     src = x.permute(1, 2, 0).contiguous()                    # NHWC input of the kernel
     out = torch.empty(C, oh, ow, device=x.device, dtype=torch.float32)
-    _lib.call("cmx_bilinear_fwd_nchw_f32", _lib.ptr(src), _lib.ptr(out), 1, H, W, oh, ow, C, 0, _lib.stream())
+    _lib.call("cmx_bilinear_fwd_nchw_f32", src, out, 1, H, W, oh, ow, C, 0)
     if as_uint8:
         out = out.round_().clamp_(0, 255)
     return out
@@ -211,8 +211,8 @@ class Evaluator(object):
             for i, (_, _, acc, sy, sx, tm) in enumerate(chunk):
                 a, b = s1[i], (s2[i] if s2 is not None else None)
                 K, ch, cw = a.shape
-                _lib.call("cmx_seg_window_accumulate", _lib.ptr(a), _lib.ptr(b), _lib.ptr(acc), K, ch, cw,
-                          tm[0], tm[1], tm[2], tm[3], acc.shape[1], acc.shape[2], sy, sx, _lib.stream())
+                _lib.call("cmx_seg_window_accumulate", a, b, acc, K, ch, cw, tm[0], tm[1], tm[2], tm[3], acc.shape[1],
+                          acc.shape[2], sy, sx)
 
     def _val_batch(self, d, x):
         """(n, 3, h, w) crops -> their logits (n, K, h, w) fp32 and (is_flip) those of the mirrored

@@ -275,7 +275,7 @@ class LayerNormResF(Function):
             sc = scale if dxs is not None else None
             if len(handed) == 3:             # a patchify conv's (dy, W, geometry): Attention.sr
                 dyc, Wc, pg = handed
-                Gc, NIg, H, Wd_, Cc, Rp, Ho, Wo = pg
+                Gc, NIg, H, Wd_, Cc = pg[:5]
                 xv = x.view(Gc * NIg, H, Wd_, Cc)
                 out = K.conv_patch_dgrad_ln_bwd(dyc, Wc, pg, xv, gamma, mean, rstd,
                                                 dres=dres_c.view_as(xv) if dres_c is not None else None,
@@ -285,8 +285,7 @@ class LayerNormResF(Function):
                     out = (out[0].view_as(x), out[1])
                 else:                        # not eligible after all: the separate patch dgrad
                     dy = torch.empty(Gc * NIg, H, Wd_, Cc, dtype=dyc.dtype, device=dyc.device)
-                    K.call("cmx_conv_patch_dgrad", K.ptr(dyc), K.ptr(Wc), K.ptr(dy), Gc, NIg, H, Wd_, Cc, Rp, Ho, Wo,
-                           Wc.shape[1], dyc.stride(0), Wc.stride(0), NIg * H * Wd_ * Cc, K.dtype_code(dyc), K.stream())
+                    K.conv_patch_dgrad(dyc, Wc, dy, pg)
                     dy, dy2 = dy.view_as(x), other
             else:
                 dz, Wd = handed
@@ -373,14 +372,9 @@ class LayerNormF(Function):
 def _layernorm_bwd_deferred(dy, x, gamma, mean, rstd, G, gg, bg):
     """dx now; dgamma / dbeta partials (G, nb, 2C) reduced by the segment's grouped reduce."""
     C = x.shape[-1]
-    R = x.numel() // C // G
-    dx = torch.empty_like(x)
-    nbytes = K.query("cmx_layernorm_bwd_workspace", R, G, C, K.dtype_code(x))
-    ws = K._ws(nbytes, x.device)
-    K.call("cmx_layernorm_bwd", K.ptr(dy), K.ptr(x), K.ptr(gamma), K.ptr(mean), K.ptr(rstd), K.ptr(dx), 0, 0,
-           K.ptr(ws), R, G, C, 0, K.dtype_code(x), K.stream())
-    nb = nbytes // (8 * G * C)
-    deferred.reduce(ws, gg, bg, G, nb, nb * 2 * C, 2 * C, 1, 2 * C, C, gg.stride(0), 0, bg.stride(0), 0)
+    dx, part = K.layernorm_bwd(dy, x, gamma, mean, rstd, G, None, None)
+    nb = part.shape[1]
+    deferred.reduce(part, gg, bg, G, nb, nb * 2 * C, 2 * C, 1, 2 * C, C, gg.stride(0), 0, bg.stride(0), 0)
     return dx
 
 
@@ -502,13 +496,12 @@ class CrossFlashAttnF(Function):
         G, M, C = q.shape
         assert G == 2 and M == B * N and kv.shape == (2, M, 2 * C) and q.is_contiguous() and kv.is_contiguous()
         dt = K.dtype_code(q)
-        esz = kv.element_size()
         o = torch.empty_like(q)
         lse = torch.empty(2, B, heads, N, dtype=torch.float32, device=q.device)
         for g in range(2):
             src = kv[1 - g]
-            K.call("cmx_sra_attn_fwd", K.ptr(q[g]), K.ptr(src), src.data_ptr() + C * esz, K.ptr(o[g]), K.ptr(lse[g]),
-                   B, N, N, heads, D, C, 2 * C, C, D ** -0.5, dt, K.stream())
+            K.call("cmx_sra_attn_fwd", q[g], src, src[:, C:], o[g], lse[g], B, N, N, heads, D, C, 2 * C, C, D ** -0.5,
+                   dt)
         ctx.save_for_backward(q, kv, o, lse)
         ctx.dims = (B, N, heads, D)
         return o
@@ -520,15 +513,13 @@ class CrossFlashAttnF(Function):
         C = heads * D
         do = _c(do)
         dt = K.dtype_code(q)
-        esz = kv.element_size()
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv)
         ws = K._ws(K.query("cmx_sra_attn_bwd_workspace", B, N, N, heads, D), q.device)
         for g in range(2):
             src, dsrc = kv[1 - g], dkv[1 - g]
-            K.call("cmx_sra_attn_bwd", K.ptr(q[g]), K.ptr(src), src.data_ptr() + C * esz, K.ptr(o[g]), K.ptr(do[g]),
-                   K.ptr(lse[g]), K.ptr(dq[g]), K.ptr(dsrc), dsrc.data_ptr() + C * esz, K.ptr(ws), B, N, N, heads, D,
-                   C, 2 * C, C, C, C, 2 * C, D ** -0.5, dt, K.stream())
+            K.call("cmx_sra_attn_bwd", q[g], src, src[:, C:], o[g], do[g], lse[g], dq[g], dsrc, dsrc[:, C:], ws, B, N,
+                   N, heads, D, C, 2 * C, C, C, C, 2 * C, D ** -0.5, dt)
         return dq, dkv, None, None, None, None
 
 
@@ -537,15 +528,14 @@ def _rowln(x, g, b, eps):
     y = torch.empty_like(x)
     mean = torch.empty(R, dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
-    K.call("cmx_rowln_fwd", K.ptr(x), K.ptr(g), K.ptr(b), K.ptr(y), K.ptr(mean), K.ptr(rstd), R, C, float(eps), K.stream())
+    K.call("cmx_rowln_fwd", x, g, b, y, mean, rstd, R, C, float(eps))
     return y, mean, rstd
 
 
 def _rowln_bwd(dy, x, g, mean, rstd, gg, gb):
     R, C = x.shape
     dx = torch.empty_like(x)
-    K.call("cmx_rowln_bwd", K.ptr(dy), K.ptr(x), K.ptr(g), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(gg), K.ptr(gb),
-           R, C, K.stream())
+    K.call("cmx_rowln_bwd", dy, x, g, mean, rstd, dx, gg, gb, R, C)
     return dx
 
 
@@ -566,26 +556,17 @@ class IFRMF(Function):
         (W1, b1, g1, e1, W3, b3, g4, e4, Wg, bgt, lc, ls, eps1, eps4) = prm["w"]
         G, B, N, C = x.shape
         dt = K.dtype_code(x)
-        f32 = dict(dtype=torch.float32, device=x.device)
-        pooled = torch.empty(B, 4 * C, **f32)
-        argmax = torch.empty(B, 2 * C, dtype=torch.int32, device=x.device)
-        ws = K._ws(K.query("cmx_frm_pool_workspace", B, N, C), x.device)
-        K.call("cmx_frm_pool_fwd", K.ptr(x), K.ptr(pooled), K.ptr(argmax), K.ptr(ws), K.ptr(pool_tickets(anchor, x, B, C)), B, N, C, dt,
-               K.stream())
-        h1 = torch.empty(B, 4 * C, **f32)
-        K.call("cmx_small_linear_fwd", K.ptr(pooled), K.ptr(W1), K.ptr(b1), K.ptr(h1), B, 4 * C, 4 * C, 0, K.stream())
+        pooled, argmax = K.frm_pool_fwd(x, pool_tickets(anchor, x, B, C))
+        h1 = K.small_linear_fwd(pooled, W1, b1, 4 * C)
         n1, m1, r1 = _rowln(h1, g1, e1, eps1)
         a1 = K.act_fwd(n1, "gelu")
-        h2 = torch.empty(B, 2 * C, **f32)
-        K.call("cmx_small_linear_fwd", K.ptr(a1), K.ptr(W3), K.ptr(b3), K.ptr(h2), B, 4 * C, 2 * C, 0, K.stream())
+        h2 = K.small_linear_fwd(a1, W3, b3, 2 * C)
         y, m2, r2 = _rowln(h2, g4, e4, eps4)
-        gt = torch.empty(B, 2 * C, **f32)
-        K.call("cmx_small_linear_fwd", K.ptr(y), K.ptr(Wg), K.ptr(bgt), K.ptr(gt), B, 2 * C, 2 * C, 3, K.stream())
-        cw = torch.empty(B, 2 * C, **f32)
-        K.call("cmx_mul2", K.ptr(y), K.ptr(gt), K.ptr(cw), B * 2 * C, K.stream())
+        gt = K.small_linear_fwd(y, Wg, bgt, 2 * C, "sigmoid")
+        cw = torch.empty(B, 2 * C, dtype=torch.float32, device=x.device)
+        K.call("cmx_mul2", y, gt, cw, B * 2 * C)
         out = torch.empty_like(x)
-        K.call("cmx_ifrm_combine_fwd", K.ptr(x), K.ptr(cw), K.ptr(sw), K.ptr(lc), K.ptr(ls), K.ptr(out), B, N, C, dt,
-               K.stream())
+        K.call("cmx_ifrm_combine_fwd", x, cw, sw, lc, ls, out, B, N, C, dt)
         ctx.save_for_backward(x, sw, pooled, argmax, h1, m1, r1, n1, a1, h2, m2, r2, y, gt, cw)
         ctx.prm = prm
         return out
@@ -604,33 +585,23 @@ class IFRMF(Function):
         nb = K.query("cmx_ifrm_combine_nblk", B, N)
         part = torch.empty(nb, 2 * C, **f32)
         lpart = torch.empty(2, nb, **f32)
-        K.call("cmx_ifrm_combine_bwd", K.ptr(dout), K.ptr(x), K.ptr(cw), K.ptr(sw), K.ptr(lc), K.ptr(ls), K.ptr(dx),
-               K.ptr(dsw), K.ptr(part), K.ptr(lpart), B, N, C, dt, K.stream())
-        K.call("cmx_partials_sum", K.ptr(lpart[0]), K.ptr(glc), 1, nb, 1, 0, 1.0, K.stream())
-        K.call("cmx_partials_sum", K.ptr(lpart[1]), K.ptr(gls), 1, nb, 1, 0, 1.0, K.stream())
-        dcw = torch.empty(B, 2 * C, **f32)
-        K.call("cmx_partials_sum", K.ptr(part), K.ptr(dcw), B, nb // B, 2 * C, 0, 1.0, K.stream())
+        K.call("cmx_ifrm_combine_bwd", dout, x, cw, sw, lc, ls, dx, dsw, part, lpart, B, N, C, dt)
+        K.partials_sum(lpart[0], glc, 1, nb, 1)
+        K.partials_sum(lpart[1], gls, 1, nb, 1)
+        dcw = K.partials_sum(part, torch.empty(B, 2 * C, **f32), B, nb // B, 2 * C)
         # cw = y * gt, gt = sigmoid(y Wg^T + bg)
         dy = torch.empty_like(y)
         dgt = torch.empty_like(gt)
-        K.call("cmx_mul2_bwd", K.ptr(dcw), K.ptr(y), K.ptr(gt), K.ptr(dy), K.ptr(dgt), B * 2 * C, K.stream())
-        ns = K.query("cmx_small_linear_nslice")
-        dyp = torch.empty(ns, B, 2 * C, **f32)
-        K.call("cmx_small_linear_bwd", K.ptr(dgt), 1, 0, 2 * C, K.ptr(gt), K.ptr(y), K.ptr(Wg), K.ptr(dyp),
-               K.ptr(gWg), K.ptr(gbg), B, 2 * C, 2 * C, 3, 0, K.stream())
-        K.call("cmx_partials_sum", K.ptr(dyp), K.ptr(dy), 1, ns, B * 2 * C, 1, 1.0, K.stream())     # dy += gate path
+        K.call("cmx_mul2_bwd", dcw, y, gt, dy, dgt, B * 2 * C)
+        dyp = K.small_linear_bwd(dgt, 1, 0, 2 * C, gt, y, Wg, gWg, gbg, 2 * C, "sigmoid")
+        K.partials_sum(dyp, dy, 1, dyp.shape[0], B * 2 * C, accumulate=True)     # dy += gate path
         dh2 = _rowln_bwd(dy, h2, g4, m2, r2, gg4, ge4)
-        dap = torch.empty(ns, B, 4 * C, **f32)
-        K.call("cmx_small_linear_bwd", K.ptr(dh2), 1, 0, 2 * C, K.ptr(h2), K.ptr(a1), K.ptr(W3), K.ptr(dap),
-               K.ptr(gW3), K.ptr(gb3), B, 4 * C, 2 * C, 0, 0, K.stream())
-        da1 = torch.empty(B, 4 * C, **f32)
-        K.call("cmx_partials_sum", K.ptr(dap), K.ptr(da1), 1, ns, B * 4 * C, 0, 1.0, K.stream())
+        dap = K.small_linear_bwd(dh2, 1, 0, 2 * C, h2, a1, W3, gW3, gb3, 2 * C)
+        da1 = K.partials_sum(dap, torch.empty(B, 4 * C, **f32), 1, dap.shape[0], B * 4 * C)
         dn1 = K.act_bwd(da1, n1, "gelu")
         dh1 = _rowln_bwd(dn1, h1, g1, m1, r1, gg1, ge1)
-        dpp = torch.empty(ns, B, 4 * C, **f32)
-        K.call("cmx_small_linear_bwd", K.ptr(dh1), 1, 0, 4 * C, K.ptr(h1), K.ptr(pooled), K.ptr(W1), K.ptr(dpp),
-               K.ptr(gW1), K.ptr(gb1), B, 4 * C, 4 * C, 0, 0, K.stream())
-        K.call("cmx_frm_pool_bwd", K.ptr(dpp), ns, B * 4 * C, K.ptr(argmax), K.ptr(dx), B, N, C, dt, K.stream())
+        dpp = K.small_linear_bwd(dh1, 1, 0, 4 * C, h1, pooled, W1, gW1, gb1, 4 * C)
+        K.frm_pool_bwd(dpp, argmax, dx)
         return dx, dsw, None, None
 
 
@@ -645,8 +616,7 @@ class DWConvF(Function):
         # LDS-tiled channel counts: also save act'(z) so the backward skips the 3x3 recompute
         tiled = C % (64 if h.dtype in (torch.bfloat16, torch.float16) else 32) == 0
         gprime = torch.empty_like(h) if tiled else None
-        K.call("cmx_dwconv3x3_fwd_save", K.ptr(h), K.ptr(w), K.ptr(b), K.ptr(out), K.ptr(gprime), NI, ipg, H, W, C,
-               K.ACT[act], K.dtype_code(h), K.stream())
+        K.call("cmx_dwconv3x3_fwd_save", h, w, b, out, gprime, NI, ipg, H, W, C, K.ACT[act], K.dtype_code(h))
         ctx.save_for_backward(h, w, b, gprime)
         ctx.meta = (wg, bg, NI, ipg, H, W, act)
         return out
@@ -657,31 +627,21 @@ class DWConvF(Function):
         wg, bg, NI, ipg, H, W, act = ctx.meta
         C = h.shape[-1]
         da = _c(da)
-        if gprime is not None:
-            dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
-            nbytes = K.query("cmx_dwconv3x3_bwd_workspace", NI, ipg, H, W, C)
-            ws = K._ws(nbytes, h.device)
-            defer = deferred.ENABLED
-            K.call("cmx_dwconv3x3_bwd_saved", K.ptr(da), K.ptr(h), K.ptr(gprime), K.ptr(w), K.ptr(dh),
-                   0 if defer else K.ptr(wg), 0 if defer else K.ptr(bg), K.ptr(ws), NI, ipg, H, W, C, 0,
-                   K.dtype_code(h), K.stream())
-            if defer:
-                G = NI // ipg
-                P = K.query("cmx_dwconv3x3_bwd_saved_tiles", ipg, H, W)
-                deferred.reduce(ws, wg, bg, G, P, P * C * 10, C * 10, C, 10, 9, wg.stride(0), 9, bg.stride(0), 1)
-            return dh, None, None, None, None, None, None, None, None, None, None
-        # the LDS-tiled backward (C % 32 == 0) keeps dz on chip; the strip path writes it
-        dz = torch.empty_like(h) if C % 32 else None
+        G, dt = NI // ipg, K.dtype_code(h)
         dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
         nbytes = K.query("cmx_dwconv3x3_bwd_workspace", NI, ipg, H, W, C)
         ws = K._ws(nbytes, h.device)
         defer = deferred.ENABLED
-        K.call("cmx_dwconv3x3_bwd", K.ptr(da), K.ptr(h), K.ptr(w), K.ptr(b), K.ptr(dz), K.ptr(dh),
-               0 if defer else K.ptr(wg), 0 if defer else K.ptr(bg), K.ptr(ws), NI, ipg, H, W, C, K.ACT[act], 0,
-               K.dtype_code(h), K.stream())
+        dw, db = (None, None) if defer else (wg, bg)
+        if gprime is not None:
+            K.call("cmx_dwconv3x3_bwd_saved", da, h, gprime, w, dh, dw, db, ws, NI, ipg, H, W, C, 0, dt)
+        else:
+            # the LDS-tiled backward (C % 32 == 0) keeps dz on chip; the strip path writes it
+            dz = torch.empty_like(h) if C % 32 else None
+            K.call("cmx_dwconv3x3_bwd", da, h, w, b, dz, dh, dw, db, ws, NI, ipg, H, W, C, K.ACT[act], 0, dt)
         if defer:       # dW / db partials (G, P, C*10) = [9 taps | bias] per channel
-            G = NI // ipg
-            P = nbytes // (40 * G * C) - 1
+            P = (K.query("cmx_dwconv3x3_bwd_saved_tiles", ipg, H, W) if gprime is not None
+                 else nbytes // (40 * G * C) - 1)
             deferred.reduce(ws, wg, bg, G, P, P * C * 10, C * 10, C, 10, 9, wg.stride(0), 9, bg.stride(0), 1)
         return dh, None, None, None, None, None, None, None, None, None, None
 
@@ -744,9 +704,8 @@ class ConvF(Function):
             dt = K.dtype_code(x)
             sk = K.query("cmx_gemm_splitk", G, M, N, Kp, 0, dt)
             ws = K._ws(K.query("cmx_gemm_workspace", G, M, N, sk), x.device) if sk > 1 else None
-            K.call("cmx_conv_implicit_fwd", K.ptr(x), K.ptr(W), K.ptr(y), K.ptr(b), K.ptr(ws), G, NIg, H, Wd, C, KH, KW,
-                   st, pad, Ho, Wo, N, NIg * H * Wd * C, W.stride(0), y.stride(0), b.stride(0) if b is not None else 0,
-                   sk, dt, K.stream())
+            K.call("cmx_conv_implicit_fwd", x, W, y, b, ws, G, NIg, H, Wd, C, KH, KW, st, pad, Ho, Wo, N,
+                   NIg * H * Wd * C, W.stride(0), y.stride(0), b.stride(0) if b is not None else 0, sk, dt)
             ctx.save_for_backward(x, W)
             ctx.meta = (Wg, bg, geom)
             ctx.xshape = x.shape
@@ -758,28 +717,22 @@ class ConvF(Function):
                 and W.shape[1] % 8 == 0 and x.dtype == torch.float32 and x.is_contiguous() \
                 and (x2 is None or x2.is_contiguous()):
             # stage 1: direct conv on the fp32 NCHW batches, no im2col columns (patch_embed1.hip)
-            Bg, N = NI // G, W.shape[1]
+            Bg = NI // G
             img1 = (x2 if x2 is not None else x[Bg:]) if G == 2 else None
-            y = torch.empty(G, Bg * Ho * Wo, N, dtype=W.dtype, device=W.device)
-            K.call("cmx_pe1_conv_fwd", K.ptr(x), K.ptr(img1), K.ptr(W), K.ptr(b), K.ptr(y), G, Bg, C, H, Wd, KH, KW,
-                   st, pad, Ho, Wo, N, Kp, W.stride(0), b.stride(0), y.stride(0), 0, 0, 0, 0, 0, 0, 0.0,
-                   K.dtype_code(W), K.stream())
+            y = K.pe1_conv_fwd(x, img1, W, b, (G, Bg, C, H, Wd, KH, KW, st, pad, Ho, Wo))
             ctx.pe1 = (x, img1)
             ctx.save_for_backward(None, W)
             ctx.meta = (Wg, bg, geom)
             return y
         cols = torch.empty(G, NI // G * Ho * Wo, Kp, dtype=W.dtype, device=W.device)
         if nchw:
-            x2 = getattr(ctx, "x2", None)
             if x2 is not None:          # (rgb, modal_x) as two batches: no concatenated copy
-                K.call("cmx_im2col_nchw2_f32", K.ptr(x), K.ptr(x2), NI - x2.shape[0], K.ptr(cols), NI, C, H, Wd, KH,
-                       KW, st, pad, Ho, Wo, Kp, K.dtype_code(cols), K.stream())
+                K.call("cmx_im2col_nchw2_f32", x, x2, NI - x2.shape[0], cols, NI, C, H, Wd, KH, KW, st, pad, Ho, Wo, Kp,
+                       K.dtype_code(cols))
             else:
-                K.call("cmx_im2col_nchw_f32", K.ptr(x), K.ptr(cols), NI, C, H, Wd, KH, KW, st, pad, Ho, Wo, Kp,
-                       K.dtype_code(cols), K.stream())
+                K.call("cmx_im2col_nchw_f32", x, cols, NI, C, H, Wd, KH, KW, st, pad, Ho, Wo, Kp, K.dtype_code(cols))
         else:
-            K.call("cmx_im2col_nhwc", K.ptr(x), K.ptr(cols), NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, Kp,
-                   K.dtype_code(cols), K.stream())
+            K.im2col_nhwc(x, cols, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo)
         y = _fwd_gemm(cols, W, b, torch.empty(G, cols.shape[1], W.shape[1], dtype=cols.dtype, device=cols.device))
         ctx.save_for_backward(cols, W)
         ctx.meta = (Wg, bg, geom)
@@ -794,22 +747,13 @@ class ConvF(Function):
         dy = _c(dy)
         if ctx.pe1 is not None:
             # per-workgroup (N, Kp + 1) partial slabs [dW | db], summed by the deferred grouped reduce
-            img0, img1 = ctx.pe1
-            Bg, N, Kp = NI // G, W.shape[1], W.shape[-1]
-            nblk = K.query("cmx_pe1_conv_wgrad_nblk", Bg, Ho, Wo)
-            ws = torch.empty(G, nblk, N, Kp + 1, dtype=torch.float32, device=dy.device)
-            K.call("cmx_pe1_conv_wgrad", K.ptr(dy), K.ptr(img0), K.ptr(img1), K.ptr(ws), G, Bg, C, H, Wd, KH, KW, st,
-                   pad, Ho, Wo, N, Kp, dy.stride(0), K.dtype_code(dy), K.stream())
-            deferred.reduce(ws, Wg, bg, G, nblk, nblk * N * (Kp + 1), N * (Kp + 1), N, Kp + 1, Kp, Wg.stride(0),
-                            Wg.stride(1), bg.stride(0), 1)
+            _pe1_wgrad(dy, ctx.pe1, Wg, bg, (G, NI // G, C, H, Wd, KH, KW, st, pad, Ho, Wo), W.shape[1], W.shape[-1])
             return None, None, None, None, None, None, None, None, None
         if ctx.implicit:
             x = cols                 # the conv input (no cols were materialised)
             if not deferred.conv_wgrad(dy, x, Wg, bg, (G, NI // G, H, Wd, C, KH, KW, st, pad, Ho, Wo)):
                 cols = torch.empty(G, NI // G * Ho * Wo, W.shape[-1], dtype=x.dtype, device=x.device)
-                K.call("cmx_im2col_nhwc", K.ptr(x), K.ptr(cols), NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, W.shape[-1],
-                       K.dtype_code(cols), K.stream())
-                _wgrad_into(dy, cols, Wg, bg)
+                _wgrad_into(dy, K.im2col_nhwc(x, cols, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo), Wg, bg)
         else:
             _wgrad_into(dy, cols, Wg, bg)
         dx = None
@@ -822,16 +766,22 @@ class ConvF(Function):
             # non-overlapping patches (Attention.sr): col2im folded into the dgrad GEMM's epilogue
             exact = H % st == 0 and Wd % st == 0
             dx = (torch.empty if exact else torch.zeros)(NI, H, Wd, C, dtype=dy.dtype, device=dy.device)
-            K.call("cmx_conv_patch_dgrad", K.ptr(dy), K.ptr(W), K.ptr(dx), G, NI // G, H, Wd, C, st, Ho, Wo, W.shape[1],
-                   dy.stride(0), W.stride(0), NI // G * H * Wd * C, K.dtype_code(dy), K.stream())
-            dx = dx.view(ctx.xshape)
+            dx = K.conv_patch_dgrad(dy, W, dx, (G, NI // G, H, Wd, C, st, Ho, Wo)).view(ctx.xshape)
         elif ctx.needs_input_grad[0] and not nchw:
             dcols = _dgrad(dy, W, torch.empty(G, NI // G * Ho * Wo, W.shape[-1], dtype=dy.dtype, device=dy.device))
             dx = torch.empty(NI, H, Wd, C, dtype=dy.dtype, device=dy.device)
-            K.call("cmx_col2im_nhwc", K.ptr(dcols), K.ptr(dx), NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, W.shape[-1],
-                   K.dtype_code(dx), K.stream())
+            K.call("cmx_col2im_nhwc", dcols, dx, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, W.shape[-1], K.dtype_code(dx))
             dx = dx.view(ctx.xshape)
         return dx, None, None, None, None, None, None, None, None
+
+
+def _pe1_wgrad(dy, imgs, Wg, bg, geom, N, Kp):
+    """The stage-1 conv's weight gradient: per-workgroup (N, Kp + 1) partial slabs [dW | db]
+    (cmx_pe1_conv_wgrad), summed by the deferred grouped reduce.  geom as K.pe1_conv_fwd's."""
+    ws = K.pe1_conv_wgrad(dy, *imgs, geom, N, Kp)
+    G, nblk = ws.shape[:2]
+    deferred.reduce(ws, Wg, bg, G, nblk, nblk * N * (Kp + 1), N * (Kp + 1), N, Kp + 1, Kp, Wg.stride(0),
+                    Wg.stride(1), bg.stride(0), 1)
 
 
 class PatchEmbed1F(Function):
@@ -845,16 +795,10 @@ class PatchEmbed1F(Function):
     @staticmethod
     def forward(ctx, x, x2, W, Wg, b, bg, gamma, beta, gg, gb, eps, geom, anchor):
         G, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo = geom
-        Bg, N, Kp = NI // G, W.shape[1], W.shape[-1]
+        Bg = NI // G
         img1 = (x2 if x2 is not None else x[Bg:]) if G == 2 else None
-        R = Bg * Ho * Wo
-        y = torch.empty(G, R, N, dtype=W.dtype, device=W.device)
-        out = torch.empty_like(y)
-        mean = torch.empty(G * R, dtype=torch.float32, device=W.device)
-        rstd = torch.empty_like(mean)
-        K.call("cmx_pe1_conv_fwd", K.ptr(x), K.ptr(img1), K.ptr(W), K.ptr(b), K.ptr(y), G, Bg, C, H, Wd, KH, KW, st,
-               pad, Ho, Wo, N, Kp, W.stride(0), b.stride(0), y.stride(0), K.ptr(gamma), K.ptr(beta), K.ptr(out),
-               K.ptr(mean), K.ptr(rstd), gamma.stride(0), float(eps), K.dtype_code(W), K.stream())
+        y, out, mean, rstd = K.pe1_conv_fwd(x, img1, W, b, (G, Bg, C, H, Wd, KH, KW, st, pad, Ho, Wo),
+                                            ln=(gamma, beta, eps))
         ctx.save_for_backward(y, gamma, mean, rstd)
         ctx.imgs = (x, img1)
         ctx.meta = (W.shape, Wg, bg, gg, gb, geom)
@@ -863,17 +807,10 @@ class PatchEmbed1F(Function):
     @staticmethod
     def backward(ctx, dout):
         y, gamma, mean, rstd = ctx.saved_tensors
-        img0, img1 = ctx.imgs
         wshape, Wg, bg, gg, gb, geom = ctx.meta
         G, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo = geom
-        Bg, N, Kp = NI // G, wshape[1], wshape[-1]
         dy = _layernorm_bwd_deferred(_c(dout), y, gamma, mean, rstd, G, gg, gb)
-        nblk = K.query("cmx_pe1_conv_wgrad_nblk", Bg, Ho, Wo)
-        ws = torch.empty(G, nblk, N, Kp + 1, dtype=torch.float32, device=dy.device)
-        K.call("cmx_pe1_conv_wgrad", K.ptr(dy), K.ptr(img0), K.ptr(img1), K.ptr(ws), G, Bg, C, H, Wd, KH, KW, st, pad,
-               Ho, Wo, N, Kp, dy.stride(0), K.dtype_code(dy), K.stream())
-        deferred.reduce(ws, Wg, bg, G, nblk, nblk * N * (Kp + 1), N * (Kp + 1), N, Kp + 1, Kp, Wg.stride(0),
-                        Wg.stride(1), bg.stride(0), 1)
+        _pe1_wgrad(dy, ctx.imgs, Wg, bg, (G, NI // G, C, H, Wd, KH, KW, st, pad, Ho, Wo), wshape[1], wshape[-1])
         return (None,) * 13
 
 
@@ -944,7 +881,7 @@ def _cross_attn_fwd(u, kv, B, N, heads, D):
     K.gemm_h2(kh.transpose(2, 3), vh.transpose(2, 3), KV, out_mode=1)          # k_h^T v_h
     P = torch.empty(GB, heads, D, D, dtype=torch.float32, device=u.device)
     ctxT = torch.empty(GB, heads, D, D, dtype=u.dtype, device=u.device)
-    K.call("cmx_ffm_ctx_fwd", K.ptr(KV), K.ptr(P), K.ptr(ctxT), G, B, heads, D, D ** -0.5, K.dtype_code(u), K.stream())
+    K.call("cmx_ffm_ctx_fwd", KV, P, ctxT, G, B, heads, D, D ** -0.5, K.dtype_code(u))
     out = torch.empty(G, M, C, dtype=u.dtype, device=u.device)
     K.gemm_h2(_heads(u, GB, N, heads, D), ctxT, _heads(out, GB, N, heads, D))  # u_h @ ctx_h (crossed)
     return out, P, ctxT
@@ -962,8 +899,7 @@ def _cross_attn_bwd(dout, u, kv, P, ctxT, B, N, heads, D, du):
     dctx = torch.empty(GB, heads, D, D, dtype=torch.float32, device=u.device)
     K.gemm_h2(_heads(u, GB, N, heads, D).transpose(2, 3), doh.transpose(2, 3), dctx, out_mode=1)   # u_h^T dout_h
     dA = torch.empty(GB, heads, D, D, dtype=u.dtype, device=u.device)
-    K.call("cmx_ffm_ctx_bwd", K.ptr(P), K.ptr(dctx), K.ptr(dA), G, B, heads, D, D ** -0.5, K.dtype_code(u),
-           K.stream())
+    K.call("cmx_ffm_ctx_bwd", P, dctx, dA, G, B, heads, D, D ** -0.5, K.dtype_code(u))
     dkv = torch.empty(G, M, 2 * C, dtype=kv.dtype, device=kv.device)
     kh, vh = _heads(kv, GB, N, heads, D), _heads(kv, GB, N, heads, D, C)
     K.gemm_h2(vh, dA, _heads(dkv, GB, N, heads, D))                            # dk_h = v_h dA_h^T
@@ -1121,16 +1057,8 @@ _POOL_TK: dict = {}
 
 
 def pool_tickets(owner, x, B, C):
-    """Zeroed arrival counters of one ChannelWeights pooling call site (cmx_frm_pool_tickets; each
-    launch leaves them zero): one set per (module -- ``owner`` is its anchor Parameter -- device,
-    size), so poolings that may run
-    concurrently (two models, two streams) never share counters.  Allocated at the first, eager
-    call (the step runs eagerly before its HIP-graph capture)."""
-    key = (id(owner), x.device, B, C)
-    t = _POOL_TK.get(key)
-    if t is None:
-        t = _POOL_TK[key] = torch.zeros(K.query("cmx_frm_pool_tickets", B, C), dtype=torch.int32, device=x.device)
-    return t
+    """Zeroed arrival counters of one ChannelWeights pooling call site (cmx_frm_pool_tickets; K.tickets)."""
+    return K.tickets(_POOL_TK, "cmx_frm_pool_tickets", owner, x, B, C)
 
 
 # test hook (tests/test_config_parity.py): a dict makes FRMF's forward record each call's
@@ -1159,16 +1087,10 @@ class FRMF(Function):
         (W1, b1, W2, b2, W0, b0, w2s, b2s) = prm["w"]
         G, B, N, C = x.shape
         dt = K.dtype_code(x)
-        pooled = torch.empty(B, 4 * C, dtype=torch.float32, device=x.device)
-        argmax = torch.empty(B, 2 * C, dtype=torch.int32, device=x.device)
-        y1 = torch.empty(B, 4 * C, dtype=torch.float32, device=x.device)
-        cw = torch.empty(B, 2 * C, dtype=torch.float32, device=x.device)
         # ChannelWeights (net_utils.py:11-30): avg || max pool + both MLP GEMVs
-        ws = K._ws(K.query("cmx_frm_pool_workspace", B, N, C), x.device)
-        K.call("cmx_frm_pool_fwd", K.ptr(x), K.ptr(pooled), K.ptr(argmax), K.ptr(ws), K.ptr(pool_tickets(anchor, x, B, C)),
-               B, N, C, dt, K.stream())
-        K.call("cmx_small_linear_fwd", K.ptr(pooled), K.ptr(W1), K.ptr(b1), K.ptr(y1), B, 4 * C, 4 * C, 2, K.stream())
-        K.call("cmx_small_linear_fwd", K.ptr(y1), K.ptr(W2), K.ptr(b2), K.ptr(cw), B, 4 * C, 2 * C, 3, K.stream())
+        pooled, argmax = K.frm_pool_fwd(x, pool_tickets(anchor, x, B, C))
+        y1 = K.small_linear_fwd(pooled, W1, b1, 4 * C, "relu")
+        cw = K.small_linear_fwd(y1, W2, b2, 2 * C, "sigmoid")
         if FRM_PROBE is not None:
             FRM_PROBE[id(anchor)] = y1.detach().clone()
         # h = cat(x1, x2) W0^T + b0 (SpatialWeights' first 1x1 conv, net_utils.py:72-73), cat-free
@@ -1177,8 +1099,7 @@ class FRMF(Function):
         h = h[0]
         sw = torch.empty(B * N, 2, dtype=torch.float32, device=x.device)
         out = torch.empty_like(x)
-        K.call("cmx_frm_combine_fwd", K.ptr(x), K.ptr(cw), K.ptr(h), K.ptr(w2s), K.ptr(b2s), K.ptr(sw), K.ptr(out), B,
-               N, C, dt, K.stream())
+        K.call("cmx_frm_combine_fwd", x, cw, h, w2s, b2s, sw, out, B, N, C, dt)
         ctx.save_for_backward(x, pooled, argmax, y1, cw, h, sw)
         ctx.prm = prm
         ctx.set_materialize_grads(False)
@@ -1203,14 +1124,13 @@ class FRMF(Function):
         dh = torch.empty_like(h)
         nb = K.query("cmx_frm_combine_bwd_nblk", N, C, dt)
         ws = K._ws(K.query("cmx_frm_combine_bwd_workspace", B, N, C, dt), x.device)
-        K.call("cmx_frm_combine_bwd", K.ptr(dout), K.ptr(dout2), K.ptr(x), K.ptr(cw), K.ptr(sw), K.ptr(h), K.ptr(w2s), K.ptr(dx),
-               K.ptr(dh), K.ptr(ws), B, N, C, dt, K.stream())
+        K.call("cmx_frm_combine_bwd", dout, dout2, x, cw, sw, h, w2s, dx, dh, ws, B, N, C, dt)
         psp = ws[B * nb * 2 * C:B * nb * 2 * C + B * nb * (2 * C + 2)]
         if deferred.ENABLED:          # [dw2 | db2] partials: weight gradients, summed by the grouped reduce
             deferred.reduce(psp, gw2s, gb2s, 1, B * nb, 0, 2 * C + 2, 1, 2 * C + 2, 2 * C, 0, 0, 0, 0)
         else:
             tmp = torch.empty(2 * C + 2, dtype=torch.float32, device=x.device)
-            K.call("cmx_partials_sum", K.ptr(psp), K.ptr(tmp), 1, B * nb, 2 * C + 2, 0, 1.0, K.stream())
+            K.partials_sum(psp, tmp, 1, B * nb, 2 * C + 2)
             gw2s.view(-1).copy_(tmp[:2 * C])
             gb2s.view(-1).copy_(tmp[2 * C:])
         # dx_g += dh @ W0[:, gC:(g+1)C] for both modalities in one launch (A = dh for both groups)
@@ -1224,18 +1144,14 @@ class FRMF(Function):
         # 1-2) it sums them itself (slab q of image m at ws[q*2C + m*nb*2C]); otherwise every one
         # of its column blocks would re-read them and one partial-sum launch is cheaper
         ns = K.query("cmx_small_linear_nslice")
-        dy1p = torch.empty(ns, B, 4 * C, dtype=torch.float32, device=x.device)
         if B * -(-2 * C // ns) * nb <= 8192:
             dcw, nsl, ss, sm = ws, nb, 2 * C, nb * 2 * C
         else:
             dcw, nsl, ss, sm = torch.empty(B, 2 * C, dtype=torch.float32, device=x.device), 1, 0, 2 * C
-            K.call("cmx_partials_sum", K.ptr(ws), K.ptr(dcw), B, nb, 2 * C, 0, 1.0, K.stream())
-        K.call("cmx_small_linear_bwd", K.ptr(dcw), nsl, ss, sm, K.ptr(cw), K.ptr(y1), K.ptr(W2), K.ptr(dy1p),
-               K.ptr(gW2), K.ptr(gb2), B, 4 * C, 2 * C, 3, 0, K.stream())
-        dpp = torch.empty(ns, B, 4 * C, dtype=torch.float32, device=x.device)
-        K.call("cmx_small_linear_bwd", K.ptr(dy1p), ns, B * 4 * C, 4 * C, K.ptr(y1), K.ptr(pooled), K.ptr(W1),
-               K.ptr(dpp), K.ptr(gW1), K.ptr(gb1), B, 4 * C, 4 * C, 2, 0, K.stream())
-        K.call("cmx_frm_pool_bwd", K.ptr(dpp), ns, B * 4 * C, K.ptr(argmax), K.ptr(dx), B, N, C, dt, K.stream())
+            K.partials_sum(ws, dcw, B, nb, 2 * C)
+        dy1p = K.small_linear_bwd(dcw, nsl, ss, sm, cw, y1, W2, gW2, gb2, 2 * C, "sigmoid")
+        dpp = K.small_linear_bwd(dy1p, ns, B * 4 * C, 4 * C, y1, pooled, W1, gW1, gb1, 4 * C, "relu")
+        K.frm_pool_bwd(dpp, argmax, dx)
         return dx, None, None
 
 
@@ -1284,35 +1200,24 @@ class BatchNormF(Function):
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         invstd = torch.empty(C, dtype=torch.float32, device=x.device)
         count = float(M)
-        small = training and group is None and M <= BN_SMALL_M and C % 16 == 0
-        if small:
-            sums = torch.empty(2, C, dtype=torch.float64, device=x.device)
-            y = torch.empty_like(x)
-            K.call("cmx_bn_small_fwd", K.ptr(x), K.ptr(res), K.ptr(gamma), K.ptr(beta), K.ptr(dscale), K.ptr(y),
-                   K.ptr(sums), K.ptr(mean), K.ptr(invstd), K.ptr(rm), K.ptr(rv), M, C, rps, K.ACT[act], eps, momentum,
-                   dt, K.stream())
-            ctx.save_for_backward(x, res if res is not None else x, mean, invstd)
-            ctx.meta = (prm, training, act, dscale, rps, group, count, res is not None)
-            ctx.small = True
-            return y
-        ctx.small = False
-        if training:
-            sums = torch.empty(2, C, dtype=torch.float64, device=x.device)
-            ws = torch.empty(max(1, K.query("cmx_bn_workspace", M, C) // 8), dtype=torch.float64, device=x.device)
-            if group is None:       # local statistics: the fold finalizes (no exchange in between)
-                K.call("cmx_bn_stats_finalize", K.ptr(x), K.ptr(sums), K.ptr(ws), M, C, eps, momentum, K.ptr(rm),
-                       K.ptr(rv), K.ptr(mean), K.ptr(invstd), dt, K.stream())
-            else:
-                K.call("cmx_bn_stats", K.ptr(x), K.ptr(sums), K.ptr(ws), M, C, dt, K.stream())
-                count = sync_bn_sums(sums, count, group)
-                K.call("cmx_bn_finalize", K.ptr(sums), count, eps, momentum, K.ptr(rm), K.ptr(rv), K.ptr(mean),
-                       K.ptr(invstd), C, 1, K.stream())
-        else:
-            K.call("cmx_bn_finalize", 0, 1.0, eps, momentum, K.ptr(rm), K.ptr(rv), K.ptr(mean), K.ptr(invstd), C, 0,
-                   K.stream())
+        ctx.small = training and group is None and M <= BN_SMALL_M and C % 16 == 0
         y = torch.empty_like(x)
-        K.call("cmx_bn_apply", K.ptr(x), K.ptr(mean), K.ptr(invstd), K.ptr(gamma), K.ptr(beta), K.ptr(res),
-               K.ptr(dscale), K.ptr(y), M, C, rps, K.ACT[act], dt, K.stream())
+        if ctx.small:
+            sums = torch.empty(2, C, dtype=torch.float64, device=x.device)
+            K.call("cmx_bn_small_fwd", x, res, gamma, beta, dscale, y, sums, mean, invstd, rm, rv, M, C, rps,
+                   K.ACT[act], eps, momentum, dt)
+        elif training:
+            sums, ws = K.bn_scratch(M, C, x.device)
+            if group is None:       # local statistics: the fold finalizes (no exchange in between)
+                K.call("cmx_bn_stats_finalize", x, sums, ws, M, C, eps, momentum, rm, rv, mean, invstd, dt)
+            else:
+                K.call("cmx_bn_stats", x, sums, ws, M, C, dt)
+                count = sync_bn_sums(sums, count, group)
+                K.call("cmx_bn_finalize", sums, count, eps, momentum, rm, rv, mean, invstd, C, 1)
+        else:
+            K.call("cmx_bn_finalize", None, 1.0, eps, momentum, rm, rv, mean, invstd, C, 0)
+        if not ctx.small:
+            K.call("cmx_bn_apply", x, mean, invstd, gamma, beta, res, dscale, y, M, C, rps, K.ACT[act], dt)
         ctx.save_for_backward(x, res if res is not None else x, mean, invstd)
         ctx.meta = (prm, training, act, dscale, rps, group, count, res is not None)
         return y
@@ -1326,25 +1231,19 @@ class BatchNormF(Function):
         M, C = x.shape
         dt = K.dtype_code(x)
         dy = _c(dy)
-        if ctx.small:
-            dx = torch.empty_like(x)
-            dres = torch.empty_like(x) if has_res else None
-            K.call("cmx_bn_small_bwd", K.ptr(dy), K.ptr(x), K.ptr(mean), K.ptr(invstd), K.ptr(gamma), K.ptr(beta),
-                   K.ptr(res), K.ptr(dscale), K.ptr(gg), K.ptr(bg), K.ptr(dx), K.ptr(dres), M, C, rps, K.ACT[act], 0,
-                   dt, K.stream())
-            return dx, dres, None, None, None, None, None, None, None
-        sums = torch.empty(2, C, dtype=torch.float64, device=x.device)
-        ws = torch.empty(max(1, K.query("cmx_bn_workspace", M, C) // 8), dtype=torch.float64, device=x.device)
-        K.call("cmx_bn_bwd_reduce", K.ptr(dy), K.ptr(x), K.ptr(mean), K.ptr(invstd), K.ptr(gamma), K.ptr(beta),
-               K.ptr(res), K.ptr(dscale), K.ptr(sums), K.ptr(gg), K.ptr(bg), K.ptr(ws), M, C, rps, K.ACT[act], 0, dt,
-               K.stream())
-        if training:
-            sync_bn_sums(sums, count, group)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if has_res else None
-        K.call("cmx_bn_bwd_apply", K.ptr(dy), K.ptr(x), K.ptr(mean), K.ptr(invstd), K.ptr(gamma), K.ptr(beta),
-               K.ptr(res), K.ptr(dscale), K.ptr(sums), count, K.ptr(dx), K.ptr(dres), M, C, rps, K.ACT[act],
-               int(training), dt, K.stream())
+        if ctx.small:
+            K.call("cmx_bn_small_bwd", dy, x, mean, invstd, gamma, beta, res, dscale, gg, bg, dx, dres, M, C, rps,
+                   K.ACT[act], 0, dt)
+            return dx, dres, None, None, None, None, None, None, None
+        sums, ws = K.bn_scratch(M, C, x.device)
+        K.call("cmx_bn_bwd_reduce", dy, x, mean, invstd, gamma, beta, res, dscale, sums, gg, bg, ws, M, C, rps,
+               K.ACT[act], 0, dt)
+        if training:
+            sync_bn_sums(sums, count, group)
+        K.call("cmx_bn_bwd_apply", dy, x, mean, invstd, gamma, beta, res, dscale, sums, count, dx, dres, M, C, rps,
+               K.ACT[act], training, dt)
         return dx, dres, None, None, None, None, None, None, None
 
 
@@ -1362,14 +1261,8 @@ _SE_TK: dict = {}
 
 
 def se_tickets(owner, x, B, C):
-    """Zeroed arrival counters of one gate's pooling (cmx_se_pool_tickets; each launch leaves them
-    zero), owned per (module -- ``owner`` is its anchor Parameter -- device, size) as pool_tickets
-    are.  Allocated at the first, eager call (the step runs eagerly before its capture)."""
-    key = (id(owner), x.device, B, C)
-    t = _SE_TK.get(key)
-    if t is None:
-        t = _SE_TK[key] = torch.zeros(max(1, K.query("cmx_se_pool_tickets", B, C)), dtype=torch.int32, device=x.device)
-    return t
+    """Zeroed arrival counters of one gate's pooling (cmx_se_pool_tickets; K.tickets)."""
+    return K.tickets(_SE_TK, "cmx_se_pool_tickets", owner, x, B, C, least=1)
 
 
 class SEGateF(Function):
@@ -1391,19 +1284,14 @@ class SEGateF(Function):
         B, N, C = y.shape
         H = W1.shape[0]
         dt = K.dtype_code(y)
-        f32 = dict(dtype=torch.float32, device=y.device)
-        pooled = torch.empty(B, C, **f32)
+        pooled = torch.empty(B, C, dtype=torch.float32, device=y.device)
         ws = K._ws(K.query("cmx_se_pool_workspace", B, N, C), y.device)
-        K.call("cmx_se_pool_fwd", K.ptr(y), K.ptr(pooled), K.ptr(ws), K.ptr(se_tickets(anchor, y, B, C)), B, N, C, dt,
-               K.stream())
-        z1 = torch.empty(B, H, **f32)
-        K.call("cmx_small_linear_fwd", K.ptr(pooled), K.ptr(W1), K.ptr(b1), K.ptr(z1), B, C, H, K.ACT["none"], K.stream())
-        h1 = torch.empty(B, H, **f32)
-        K.call("cmx_act_fwd", K.ptr(z1), K.ptr(h1), B * H, K.ACT["gelu"], 0, K.stream())
-        a = torch.empty(B, C, **f32)
-        K.call("cmx_small_linear_fwd", K.ptr(h1), K.ptr(W2), K.ptr(b2), K.ptr(a), B, H, C, K.ACT["sigmoid"], K.stream())
+        K.call("cmx_se_pool_fwd", y, pooled, ws, se_tickets(anchor, y, B, C), B, N, C, dt)
+        z1 = K.small_linear_fwd(pooled, W1, b1, H)
+        h1 = K.act_fwd(z1, "gelu")
+        a = K.small_linear_fwd(h1, W2, b2, C, "sigmoid")
         out = torch.empty_like(y)
-        K.call("cmx_se_scale_fwd", K.ptr(y), K.ptr(a), K.ptr(dscale), K.ptr(out), B, N, C, dt, K.stream())
+        K.call("cmx_se_scale_fwd", y, a, dscale, out, B, N, C, dt)
         ctx.save_for_backward(y, a, z1, pooled)
         ctx.meta = (prm, dscale)
         return out
@@ -1421,23 +1309,14 @@ class SEGateF(Function):
         dout = _c(dout)
         nda = K.query("cmx_se_bwd_nslice", B, N, C)
         dap = torch.empty(nda, B, C, **f32)
-        K.call("cmx_se_bwd_reduce", K.ptr(dout), K.ptr(y), K.ptr(dscale), K.ptr(dap), B, N, C, dt, K.stream())
-        h1 = torch.empty(B, H, **f32)                 # GELU(z1) again: (B, C/4) values
-        K.call("cmx_act_fwd", K.ptr(z1), K.ptr(h1), B * H, K.ACT["gelu"], 0, K.stream())
-        ns = K.query("cmx_small_linear_nslice")
-        dh1p = torch.empty(ns, B, H, **f32)
-        K.call("cmx_small_linear_bwd", K.ptr(dap), nda, B * C, C, K.ptr(a), K.ptr(h1), K.ptr(W2), K.ptr(dh1p),
-               K.ptr(gW2), K.ptr(gb2), B, H, C, K.ACT["sigmoid"], 0, K.stream())
-        dh1 = torch.empty(B, H, **f32)
-        K.call("cmx_partials_sum", K.ptr(dh1p), K.ptr(dh1), 1, ns, B * H, 0, 1.0, K.stream())
-        dz1 = torch.empty(B, H, **f32)
-        K.call("cmx_act_bwd", K.ptr(dh1), K.ptr(z1), K.ptr(dz1), B * H, K.ACT["gelu"], 0, K.stream())
-        dpp = torch.empty(ns, B, C, **f32)
-        K.call("cmx_small_linear_bwd", K.ptr(dz1), 1, 0, H, K.ptr(z1), K.ptr(pooled), K.ptr(W1), K.ptr(dpp),
-               K.ptr(gW1), K.ptr(gb1), B, C, H, K.ACT["none"], 0, K.stream())
+        K.call("cmx_se_bwd_reduce", dout, y, dscale, dap, B, N, C, dt)
+        h1 = K.act_fwd(z1, "gelu")                    # GELU(z1) again: (B, C/4) values
+        dh1p = K.small_linear_bwd(dap, nda, B * C, C, a, h1, W2, gW2, gb2, C, "sigmoid")
+        dh1 = K.partials_sum(dh1p, torch.empty(B, H, **f32), 1, dh1p.shape[0], B * H)
+        dz1 = K.act_bwd(dh1, z1, "gelu")
+        dpp = K.small_linear_bwd(dz1, 1, 0, H, z1, pooled, W1, gW1, gb1, H)
         dy = torch.empty_like(y)
-        K.call("cmx_se_bwd_apply", K.ptr(dout), K.ptr(a), K.ptr(dscale), K.ptr(dpp), ns, B * C, K.ptr(dy), B, N, C, dt,
-               K.stream())
+        K.call("cmx_se_bwd_apply", dout, a, dscale, dpp, dpp.shape[0], B * C, dy, B, N, C, dt)
         return dy, None, None, None
 
 
@@ -1456,13 +1335,10 @@ def se_gate(store, att, y, dscale=None):
 def _adjoint_to(dZ, B, H1, W1, h, w, E):
     """up^T dZ: the bilinear adjoint of the (h, w) -> (H1, W1) upsample, (B, h*w, E) in dZ's
     dtype (two separable 1-D gather passes, fp32 in between, no atomics)."""
-    dt = K.dtype_code(dZ)
     tmp = torch.empty(B * H1, w, E, dtype=torch.float32, device=dZ.device)
-    K.call("cmx_bilinear_adjoint_1d", K.ptr(dZ), K.ptr(tmp), B * H1, W1, w, E, W1 * E, E, 0, 0, 1.0, dt, 0, K.stream())
+    K.bilinear_adjoint_1d(dZ, tmp, B * H1, W1, w, E, W1 * E, E)
     g = torch.empty(B, h * w, E, dtype=dZ.dtype, device=dZ.device)
-    K.call("cmx_bilinear_adjoint_1d", K.ptr(tmp), K.ptr(g), B, H1, h, w * E, H1 * w * E, w * E, 0, 0, 1.0, 0, dt,
-           K.stream())
-    return g
+    return K.bilinear_adjoint_1d(tmp, g, B, H1, h, w * E, H1 * w * E, w * E)
 
 
 class DecoderFuseF(Function):
@@ -1512,11 +1388,7 @@ def _decoder_fuse_fwd(ctx, slots, e4, e3, e2, e1, Wf, Wfg, bf, bfg, sizes):
         jobs.append(dict(A=e.reshape(1, B * h * w, E), B=W[None, :, slot * E:(slot + 1) * E], C=z))
         zs.append(z)
     _gemm_group(jobs)                         # the three branch products: one launch
-    Z = torch.empty(B * N1, E, dtype=e1.dtype, device=e1.device)
-    Wc1 = W[:, slots[3] * E:(slots[3] + 1) * E]
-    K.call("cmx_decoder_fuse_fwd", K.ptr(_c(e1)), Wc1.data_ptr(), K.ptr(Z), K.ptr(bf), K.ptr(zs[0]), K.ptr(zs[1]),
-           K.ptr(zs[2]), B, H1, W1, hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, E, E,
-           W.stride(0), K.dtype_code(e1), K.stream())
+    Z = K.decoder_fuse_fwd(_c(e1), W[:, slots[3] * E:(slots[3] + 1) * E], bf, zs, H1, W1, hw)
     ctx.save_for_backward(e4, e3, e2, e1, Wf)
     ctx.meta = (Wfg, bfg, sizes, slots)
     return Z
@@ -1629,8 +1501,7 @@ def _decoder_fold_fwd(ctx, slots, x4, x3, x2, x1, Wf, Wc, bf, bc, grads, sizes):
     _gemm_group([dict(A=Wf[None, :, s * E:(s + 1) * E], B=Wc[s][None].transpose(1, 2), C=Ms[s], splitk=1)
                  for s in range(4)])          # M_i = Wf_i Wc_i: one launch
     b = torch.empty(E, dtype=torch.float32, device=Wf.device)
-    K.call("cmx_decoder_fold_bias", Wf.data_ptr(), Wf.stride(0), K.ptr(bf), *[K.ptr(t) for t in bc], K.ptr(b), E,
-           K.dtype_code(Wf), K.stream())
+    K.call("cmx_decoder_fold_bias", Wf, Wf.stride(0), bf, *bc, b, E, K.dtype_code(Wf))
     zs, jobs = [], []
     for j, (h, w) in enumerate((hw[2], hw[1], hw[0])):
         s = slots[j]
@@ -1638,17 +1509,15 @@ def _decoder_fold_fwd(ctx, slots, x4, x3, x2, x1, Wf, Wc, bf, bc, grads, sizes):
         jobs.append(dict(A=_c(xs[j]).reshape(1, B * h * w, Cs[s]), B=Ms[s], C=z))
         zs.append(z)
     _gemm_group(jobs)                         # the three low-resolution branch products: one launch
-    Z = torch.empty(B * N1, E, dtype=x1.dtype, device=x1.device)
     if _up3_ok(E, [w for (_, w) in hw]):
         # b + the three upsampled products in one pass, then the c1 GEMM with it as the residual
+        Z = torch.empty(B * N1, E, dtype=x1.dtype, device=x1.device)
         U = torch.empty(1, B * N1, E, dtype=x1.dtype, device=x1.device)
-        K.call("cmx_bilinear_up3_add", K.ptr(zs[0]), K.ptr(zs[1]), K.ptr(zs[2]), B, hw[2][0], hw[2][1], hw[1][0],
-               hw[1][1], hw[0][0], hw[0][1], K.ptr(b), K.ptr(U), H1, W1, E, K.dtype_code(x1), K.stream())
+        K.call("cmx_bilinear_up3_add", zs[0], zs[1], zs[2], B, *hw[2], *hw[1], *hw[0], b, U, H1, W1, E,
+               K.dtype_code(x1))
         K.gemm(_c(x1).view(1, B * N1, C1), Ms[slots[3]], Z.view(1, B * N1, E), residual=U)
     else:
-        K.call("cmx_decoder_fuse_fwd", K.ptr(_c(x1)), K.ptr(Ms[slots[3]]), K.ptr(Z), K.ptr(b), K.ptr(zs[0]), K.ptr(zs[1]),
-               K.ptr(zs[2]), B, H1, W1, hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, C1, C1, C1,
-               K.dtype_code(x1), K.stream())
+        Z = K.decoder_fuse_fwd(_c(x1), Ms[slots[3]][0], b, zs, H1, W1, hw)
     ctx.save_for_backward(*xs, Wf, *Wc, *Ms)
     ctx.meta = (bc, grads, sizes, _adj3_ok(E, W1, [w for (_, w) in hw], x1.dtype), slots)
     return Z
@@ -1672,8 +1541,7 @@ def _decoder_fold_bwd(ctx, dZ):
         # the three grids' bilinear adjoints from one read of dZ (cmx_bilinear_adjoint3)
         dYs = [torch.empty(1, B * h * w, E, dtype=dZ.dtype, device=dZ.device) for (h, w) in (hw[2], hw[1], hw[0])]
         ts = [torch.empty(B * H1 * w * E, dtype=torch.float32, device=dZ.device) for (h, w) in (hw[2], hw[1], hw[0])]
-        K.call("cmx_bilinear_adjoint3", K.ptr(dZ), *[K.ptr(t) for t in ts], *[K.ptr(y) for y in dYs], B, H1, W1,
-               hw[2][0], hw[2][1], hw[1][0], hw[1][1], hw[0][0], hw[0][1], E, K.dtype_code(dZ), K.stream())
+        K.call("cmx_bilinear_adjoint3", dZ, *ts, *dYs, B, H1, W1, *hw[2], *hw[1], *hw[0], E, K.dtype_code(dZ))
     dxs, jobs = [], []
     for j in range(4):
         s = slots[j]
@@ -1699,9 +1567,8 @@ def _decoder_fold_chain(dM, gb, offs, Wf, Wc, bc, grads, Cs, E):
     h16 = Wf.dtype != torch.float32
     dMh = torch.empty(dM.shape, dtype=Wf.dtype, device=dM.device) if h16 else None
     WfT = torch.empty(4 * E, E, dtype=Wf.dtype, device=Wf.device)
-    K.call("cmx_decoder_fold_bwd_prep", K.ptr(dM), K.ptr(dMh), dM.numel(), K.ptr(gb), Wf.data_ptr(), Wf.stride(0),
-           K.ptr(WfT), Wfg.data_ptr(), Wfg.stride(-2), *[K.ptr(t) for t in bc], *[K.ptr(t) for t in bcg], K.ptr(bfg),
-           E, K.dtype_code(Wf), K.stream())
+    K.call("cmx_decoder_fold_bwd_prep", dM, dMh, dM.numel(), gb, Wf, Wf.stride(0), WfT, Wfg, Wfg.stride(-2), *bc, *bcg,
+           bfg, E, K.dtype_code(Wf))
     src = dMh if h16 else dM
     D = [src[offs[s]:offs[s + 1]].view(1, E, Cs[s]) for s in range(4)]
     # dWf_i += dM_i Wc_i^T (onto gb bc_i^T) and dWc_i = Wf_i^T dM_i: one launch each
@@ -1714,8 +1581,7 @@ def _decoder_fold_chain(dM, gb, offs, Wf, Wc, bc, grads, Cs, E):
 def _scale_adjoint(ctx, adj, dloss, out):
     """The backward of the forward-adjoint losses: dlogits = adj * dloss / normaliser (out[1])."""
     dl = torch.empty(ctx.lshape, dtype=ctx.ldtype, device=adj.device)
-    K.call("cmx_upsample_ce_bwd_scale", K.ptr(adj), K.ptr(dloss), K.ptr(out), K.ptr(dl), dl.numel(),
-           K.dtype_code(dl), K.stream())
+    K.call("cmx_upsample_ce_bwd_scale", adj, dloss, out, dl, dl.numel(), K.dtype_code(dl))
     return dl
 
 
@@ -1736,13 +1602,12 @@ class UpsampleCEF(Function):
         ws = K._ws(K.query("cmx_upsample_ce_workspace", B, H, W), logits.device)
         if fused and ctx.needs_input_grad[0]:
             adj = torch.empty(B, h * w, Kc, dtype=torch.float32, device=logits.device)
-            K.call("cmx_upsample_ce_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(adj), K.ptr(out), K.ptr(ws), B, h, w,
-                   H, W, Kc, ignore, K.dtype_code(logits), K.stream())
+            K.call("cmx_upsample_ce_fwd_adj", logits, label, adj, out, ws, B, h, w, H, W, Kc, ignore,
+                   K.dtype_code(logits))
             ctx.save_for_backward(adj, out, label)
             ctx.fused, ctx.ldtype, ctx.lshape = "adj", logits.dtype, logits.shape
             return out[0]
-        K.call("cmx_upsample_ce_fwd", K.ptr(logits), K.ptr(label), K.ptr(grad), K.ptr(out), K.ptr(ws), B, h, w, H,
-               W, Kc, ignore, K.dtype_code(logits), K.stream())
+        K.call("cmx_upsample_ce_fwd", logits, label, grad, out, ws, B, h, w, H, W, Kc, ignore, K.dtype_code(logits))
         ctx.save_for_backward(logits if fused else grad, out, label)
         ctx.fused = fused
         ctx.dims = dims
@@ -1760,11 +1625,9 @@ class UpsampleCEF(Function):
         # autograd never comes here for it)
         B, h, w, H, W, Kc = ctx.dims
         tmp = torch.empty(B * H, w, Kc, dtype=torch.float32, device=grad.device)
-        K.call("cmx_bilinear_adjoint_1d", K.ptr(grad), K.ptr(tmp), B * H, W, w, Kc, W * Kc, Kc, 0, 0, 1.0,
-               K.dtype_code(grad), 0, K.stream())
+        K.bilinear_adjoint_1d(grad, tmp, B * H, W, w, Kc, W * Kc, Kc)
         dl = torch.empty(B, h * w, Kc, dtype=ctx.ldtype, device=grad.device)
-        K.call("cmx_bilinear_adjoint_1d", K.ptr(tmp), K.ptr(dl), B, H, h, w * Kc, H * w * Kc, w * Kc, K.ptr(dloss),
-               out.data_ptr() + 4, 1.0, 0, K.dtype_code(dl), K.stream())
+        K.bilinear_adjoint_1d(tmp, dl, B, H, h, w * Kc, H * w * Kc, w * Kc, a1=dloss, a2=out[1:])
         return dl.view(ctx.lshape), None, None, None
 
 
@@ -1791,14 +1654,11 @@ class UpsampleLossF(Function):
         out = torch.empty(3, dtype=torch.float32, device=logits.device)
         adj = torch.empty(B, h * w, Kc, dtype=torch.float32, device=logits.device)
         ws = K._ws(K.query("cmx_upsample_loss_workspace", B, h, w), logits.device)
-        st = K._lib.try_call("cmx_upsample_loss_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(weight), K.ptr(adj),
-                           K.ptr(out), K.ptr(ws), B, h, w, H, W, Kc, ignore, int(kind), float(gamma), float(alpha),
-                           float(ce_scale), float(focal_scale), K.dtype_code(logits), K.stream())
-        if st == K._lib.CMX_ERR_SHAPE:
-            raise NotImplementedError(f"fused upsample + loss: {K._lib.last_error()}; only CrossEntropyLoss has a "
+        if K.refusable("cmx_upsample_loss_fwd_adj", (K.CMX_ERR_SHAPE,), logits, label, weight, adj, out, ws, B, h, w, H,
+                       W, Kc, ignore, int(kind), float(gamma), float(alpha), float(ce_scale), float(focal_scale),
+                       K.dtype_code(logits)) is K.REFUSED:
+            raise NotImplementedError(f"fused upsample + loss: {K.last_error()}; only CrossEntropyLoss has a "
                                       "materialised path for other shapes")
-        if st != 0:
-            raise K._lib.CMXError(f"cmx_upsample_loss_fwd_adj failed ({st}): {K._lib.last_error()}")
         ctx.save_for_backward(adj, out)
         ctx.ldtype, ctx.lshape = logits.dtype, logits.shape
         return out[0]             # a view of the kernel's result (no copy launch)
@@ -1829,14 +1689,11 @@ class UpsampleDiceF(Function):
         stats = torch.empty(B, Kc, 3, **f32)
         adj = torch.empty(B, h * w, Kc, **f32) if ctx.needs_input_grad[0] else None
         ws = K._ws(K.query("cmx_upsample_dice_workspace", B, h, w, Kc), logits.device)
-        st = K._lib.try_call("cmx_upsample_dice_fwd_adj", K.ptr(logits), K.ptr(label), K.ptr(adj), K.ptr(out),
-                             K.ptr(stats), K.ptr(ws), B, h, w, H, W, Kc, ignore, float(ce_scale), float(dice_scale),
-                             float(smooth), K.dtype_code(logits), K.stream())
-        if st == K._lib.CMX_ERR_SHAPE:
-            raise NotImplementedError(f"fused upsample + Dice loss: {K._lib.last_error()}; only CrossEntropyLoss has "
+        if K.refusable("cmx_upsample_dice_fwd_adj", (K.CMX_ERR_SHAPE,), logits, label, adj, out, stats, ws, B, h, w, H,
+                       W, Kc, ignore, float(ce_scale), float(dice_scale), float(smooth),
+                       K.dtype_code(logits)) is K.REFUSED:
+            raise NotImplementedError(f"fused upsample + Dice loss: {K.last_error()}; only CrossEntropyLoss has "
                                       "a materialised path for other shapes")
-        if st != 0:
-            raise K._lib.CMXError(f"cmx_upsample_dice_fwd_adj failed ({st}): {K._lib.last_error()}")
         ctx.save_for_backward(adj, out)
         ctx.ldtype, ctx.lshape = logits.dtype, logits.shape
         return out[0]             # a view of the kernel's result (no copy launch)
@@ -1850,6 +1707,5 @@ class UpsampleDiceF(Function):
 
 def upsample_logits_nchw(logits, B, h, w, H, W, Kc):
     out = torch.empty(B, Kc, H, W, dtype=torch.float32, device=logits.device)
-    K.call("cmx_bilinear_fwd_nchw_f32", K.ptr(_c(logits)), K.ptr(out), B, h, w, H, W, Kc, K.dtype_code(logits),
-           K.stream())
+    K.call("cmx_bilinear_fwd_nchw_f32", _c(logits), out, B, h, w, H, W, Kc, K.dtype_code(logits))
     return out

@@ -1,4 +1,6 @@
-"""Tensor-level wrappers over the C-ABI (one function per entry point group).
+"""Tensor-level wrappers over the C-ABI, one per entry point (or short protocol) that the package
+calls from two or more places; a single-use entry point is called through ``call`` in the header's
+argument order (_lib: a tensor, None or an integer address per pointer; the trailing stream is filled).
 
 Every function launches on torch's current stream, allocates outputs/workspaces through
 torch's caching allocator (so HIP-graph capture works) and raises CMXError on failure.
@@ -8,11 +10,11 @@ from __future__ import annotations
 
 import collections
 import ctypes
-import math
 import torch
 
 from . import _lib
-from ._lib import call, query, ptr, stream, dtype_code
+from ._lib import (call, try_call, query, refusable, last_error, ptr, stream, dtype_code,  # noqa: F401
+                   REFUSED, CMX_ERR_ARG, CMX_ERR_SHAPE)
 
 ACT = {"none": 0, "gelu": 1, "relu": 2, "sigmoid": 3}
 
@@ -31,6 +33,17 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
 
 
+def tickets(cache: dict, entry: str, owner, x, B, C, least: int = 0) -> torch.Tensor:
+    """Zeroed arrival counters (``entry``(B, C) of them, at least ``least``; each launch leaves them zero): one set in
+    ``cache`` per (module -- ``owner`` is its anchor Parameter -- device, size), so launches that may run concurrently
+    (two models, two streams) never share them.  Allocated at the first, eager call (before any HIP-graph capture)."""
+    key = (id(owner), x.device, B, C)
+    t = cache.get(key)
+    if t is None:
+        t = cache[key] = torch.zeros(max(least, query(entry, B, C)), dtype=torch.int32, device=x.device)
+    return t
+
+
 # ------------------------------------------------------------------------------ LayerNorm
 def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, G: int = 1,
                   save_stats: bool = True):
@@ -41,21 +54,26 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
     y = torch.empty_like(x)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device) if save_stats else None
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if save_stats else None
-    call("cmx_layernorm_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), R, G, C,
-         float(eps), dtype_code(x), stream())
+    call("cmx_layernorm_fwd", x, gamma, beta, y, mean, rstd, R, G, C, float(eps), dtype_code(x))
     return y, mean, rstd
 
 
-def layernorm_bwd(dy, x, gamma, mean, rstd, G: int, dgamma: torch.Tensor, dbeta: torch.Tensor,
-                  accumulate: bool = False):
+def _ln_bwd_buffers(x, G):
+    """(R, C, dx, workspace, the workspace seen as (G, nb, 2C) = [dgamma | dbeta] partials per block)."""
     C = x.shape[-1]
-    rows = x.numel() // C
-    R = rows // G
-    dx = torch.empty_like(x)
-    ws = _ws(query("cmx_layernorm_bwd_workspace", R, G, C, dtype_code(x)), x.device)
-    call("cmx_layernorm_bwd", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dgamma),
-         ptr(dbeta), ptr(ws), R, G, C, int(accumulate), dtype_code(x), stream())
-    return dx
+    R = x.numel() // C // G
+    nbytes = query("cmx_layernorm_bwd_workspace", R, G, C, dtype_code(x))
+    ws = _ws(nbytes, x.device)
+    nb = nbytes // (8 * G * C)
+    return R, C, torch.empty_like(x), ws, ws[:G * nb * 2 * C].view(G, nb, 2 * C)
+
+
+def layernorm_bwd(dy, x, gamma, mean, rstd, G: int, dgamma: torch.Tensor | None, dbeta: torch.Tensor | None,
+                  accumulate: bool = False):
+    """Returns dx; with dgamma = dbeta = None (the deferred mode) (dx, partials) as layernorm_bwd_res does."""
+    R, C, dx, ws, part = _ln_bwd_buffers(x, G)
+    call("cmx_layernorm_bwd", dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, R, G, C, accumulate, dtype_code(x))
+    return dx if dgamma is not None or dbeta is not None else (dx, part)
 
 
 def layernorm_bwd_res(dy, x, gamma, mean, rstd, G: int, dgamma=None, dbeta=None, dy2=None, dres=None, sscale=None,
@@ -64,56 +82,47 @@ def layernorm_bwd_res(dy, x, gamma, mean, rstd, G: int, dgamma=None, dbeta=None,
     (dy2 / dres / sscale / dxs optional; dxs is the caller's).  Returns (dx, partials): with dgamma = dbeta =
     None nothing is reduced and partials, the workspace seen as (G, nb, 2C) = [dgamma | dbeta] per block,
     is what the caller reduces (the deferred mode)."""
-    C = x.shape[-1]
-    rows = x.numel() // C
-    R = rows // G
-    dx = torch.empty_like(x)
-    nbytes = query("cmx_layernorm_bwd_workspace", R, G, C, dtype_code(x))
-    ws = _ws(nbytes, x.device)
-    call("cmx_layernorm_bwd_res", ptr(dy), ptr(dy2), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres),
-         ptr(sscale), ptr(dxs), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), R, G, C, int(rows_per_sample),
-         int(accumulate), dtype_code(x), stream())
-    nb = nbytes // (8 * G * C)
-    return dx, ws[:G * nb * 2 * C].view(G, nb, 2 * C)
+    R, C, dx, ws, part = _ln_bwd_buffers(x, G)
+    call("cmx_layernorm_bwd_res", dy, dy2, x, gamma, mean, rstd, dres, sscale, dxs, dx, dgamma, dbeta, ws, R, G, C,
+         int(rows_per_sample), accumulate, dtype_code(x))
+    return dx, part
 
 
 # ------------------------------------------------------------------------------ elementwise
 def residual_add(x, y, sample_scale=None, out=None, n_per_sample=None):
     out = torch.empty_like(x) if out is None else out
     nps = n_per_sample if n_per_sample is not None else x.numel()
-    call("cmx_residual_add", ptr(x), ptr(y), ptr(sample_scale), ptr(out), nps, x.numel(),
-         dtype_code(x), stream())
+    call("cmx_residual_add", x, y, sample_scale, out, nps, x.numel(), dtype_code(x))
     return out
 
 
 def scale_samples(x, sample_scale, n_per_sample, out=None):
     out = torch.empty_like(x) if out is None else out
-    call("cmx_scale_samples", ptr(x), ptr(sample_scale), ptr(out), n_per_sample, x.numel(),
-         dtype_code(x), stream())
+    call("cmx_scale_samples", x, sample_scale, out, n_per_sample, x.numel(), dtype_code(x))
     return out
 
 
 def act_fwd(x, act: str, out=None):
     out = torch.empty_like(x) if out is None else out
-    call("cmx_act_fwd", ptr(x), ptr(out), x.numel(), ACT[act], dtype_code(x), stream())
+    call("cmx_act_fwd", x, out, x.numel(), ACT[act], dtype_code(x))
     return out
 
 
 def act_bwd(dy, z, act: str, out=None):
     out = torch.empty_like(dy) if out is None else out
-    call("cmx_act_bwd", ptr(dy), ptr(z), ptr(out), dy.numel(), ACT[act], dtype_code(dy), stream())
+    call("cmx_act_bwd", dy, z, out, dy.numel(), ACT[act], dtype_code(dy))
     return out
 
 
 def cast_f32_bf16(src: torch.Tensor, dst: torch.Tensor):
     assert src.dtype == torch.float32 and dst.dtype == torch.bfloat16 and src.numel() == dst.numel()
-    call("cmx_cast_f32_bf16", ptr(src), ptr(dst), src.numel(), stream())
+    call("cmx_cast_f32_bf16", src, dst, src.numel())
 
 
 def cast_f32_h16(src: torch.Tensor, dst: torch.Tensor):
     """fp32 -> bf16 / fp16 (round to nearest even) into ``dst``'s dtype."""
     assert src.dtype == torch.float32 and dst.dtype in (torch.bfloat16, torch.float16) and src.numel() == dst.numel()
-    call("cmx_cast_f32_h16", ptr(src), ptr(dst), src.numel(), dtype_code(dst), stream())
+    call("cmx_cast_f32_h16", src, dst, src.numel(), dtype_code(dst))
     return dst
 
 
@@ -124,19 +133,47 @@ def colsum(x: torch.Tensor, out: torch.Tensor, G: int = 1, accumulate: bool = Fa
     N = N if N is not None else x.shape[-1]
     M = x.shape[:-1].numel() // G
     ws = _ws(query("cmx_colsum_workspace", M, G, N), x.device)
-    call("cmx_colsum", ptr(x), ptr(out), ptr(ws), M, G, N, ld, int(accumulate), float(alpha),
-         dtype_code(x), stream())
+    call("cmx_colsum", x, out, ws, M, G, N, ld, accumulate, float(alpha), dtype_code(x))
     return out
 
 
+def partials_sum(part: torch.Tensor, out: torch.Tensor, G: int, nblk: int, W: int, accumulate: bool = False):
+    """out (G, W) fp32 (+)= the sum of the nblk partial rows of part (G, nblk, W) (cmx_partials_sum)."""
+    call("cmx_partials_sum", part, out, G, nblk, W, accumulate, 1.0)
+    return out
+
+
+# ------------------------------------------------------------------------------ tiny-M linear (fp32 GEMV chains)
+def small_linear_fwd(x: torch.Tensor, W, b, Nout: int, act: str = "none") -> torch.Tensor:
+    """y (M, Nout) fp32 = act(x W^T + b) on x (M, K) fp32, M <= 8 (cmx_small_linear_fwd)."""
+    M, Kin = x.shape
+    y = torch.empty(M, Nout, dtype=torch.float32, device=x.device)
+    call("cmx_small_linear_fwd", x, W, b, y, M, Kin, Nout, ACT[act])
+    return y
+
+
+def small_linear_bwd(dy_part, nslice: int, slice_stride: int, row_stride: int, y, x, W, dW, db, Nout: int,
+                     act: str = "none") -> torch.Tensor:
+    """small_linear_fwd's backward (cmx_small_linear_bwd): dy[m][n] = sum_s dy_part[s * slice_stride + m * row_stride
+    + n] over nslice slabs; writes dW / db, returns dx as cmx_small_linear_nslice() partial slices (ns, M, K)."""
+    M, Kin = x.shape
+    dx_part = torch.empty(query("cmx_small_linear_nslice"), M, Kin, dtype=torch.float32, device=x.device)
+    call("cmx_small_linear_bwd", dy_part, nslice, slice_stride, row_stride, y, x, W, dx_part, dW, db, M, Kin, Nout,
+         ACT[act], 0)
+    return dx_part
+
+
 # ------------------------------------------------------------------------------ GEMM
-def _operand(t: torch.Tensor, name: str):
-    """(G, rows, k) logical view -> (trans, ld, batch stride)."""
+def _operand(t: torch.Tensor, name: str | None = None):
+    """(G, rows, k) logical view -> (trans, ld, batch stride); with neither stride a unit one: None, or the
+    ValueError of a caller that names the operand."""
     if t.stride(2) == 1:
         return 0, t.stride(1), t.stride(0)
     if t.stride(1) == 1:
         return 1, t.stride(2), t.stride(0)
-    raise ValueError(f"gemm: operand {name} needs a unit stride along rows or k, got strides {t.stride()}")
+    if name is not None:
+        raise ValueError(f"gemm: operand {name} needs a unit stride along rows or k, got strides {t.stride()}")
+    return None
 
 
 def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, bias: torch.Tensor | None = None,
@@ -179,21 +216,20 @@ def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, bias: torch.Tensor |
         assert mask.shape == C.shape and mask.stride() == C.stride() and mask.dtype == C.dtype and out_mode == 0
     Nk = N + (1 if dbias is not None else 0)
     if splitk <= 0:
-        splitk = query("cmx_gemm_splitk", G, M, Nk, Kd, int(dbias is not None), dtype_code(A))
+        splitk = query("cmx_gemm_splitk", G, M, Nk, Kd, dbias is not None, dtype_code(A))
     args = (G, M, Nk, Kd, K1, lda, lda2, ldb, C.stride(1), sA, sA2, sB, C.stride(0), sbias, sdb, int(rows_per_sample),
-            tA, tB, ACT[act], int(out_mode), int(dbias is not None), int(splitk), dtype_code(A))
+            tA, tB, ACT[act], int(out_mode), dbias is not None, int(splitk), dtype_code(A))
     if plan:
         if splitk > 1:
             return None
         rec = (ctypes.c_uint8 * _PLAN_BYTES)()
-        nb = query("cmx_gemm_plan", ctypes.addressof(rec), ptr(A), ptr(A2), ptr(B), ptr(C), ptr(bias), ptr(residual),
-                   ptr(rscale), ptr(mask), ptr(dbias), 0, *args)
+        nb = query("cmx_gemm_plan", ctypes.addressof(rec), A, A2, B, C, bias, residual, rscale, mask, dbias, None,
+                   *args)
         if nb < 0:
             raise _lib.CMXError(f"cmx_gemm_plan failed ({nb}): {_lib.last_error()}")
         return GemmPlan(rec, (A, A2, B, C, bias, residual, rscale, mask)) if nb > 0 else None
     ws = _ws(query("cmx_gemm_workspace", G, M, Nk, splitk), A.device) if splitk > 1 else None
-    call("cmx_gemm", ptr(A), ptr(A2), ptr(B), ptr(C), ptr(bias), ptr(residual), ptr(rscale), ptr(mask), ptr(dbias),
-         ptr(ws), *args, stream())
+    call("cmx_gemm", A, A2, B, C, bias, residual, rscale, mask, dbias, ws, *args)
     return C
 
 
@@ -217,14 +253,11 @@ def gemm_ln(A, B, C, ln_gamma, ln_beta, ln_eps, bias=None, residual=None, rscale
     y = torch.empty_like(C)
     mean = torch.empty(G, M, dtype=torch.float32, device=C.device)
     rstd = torch.empty_like(mean)
-    st = _lib.try_call("cmx_gemm_ln", ptr(A), ptr(A2), ptr(B), ptr(C), ptr(bias), ptr(residual), ptr(rscale), G, M, N, Kd, K1,
-                         lda, lda2, ldb, C.stride(1), sA, sA2, sB, C.stride(0), sbias, int(rows_per_sample), ACT[act],
-                         ptr(ln_gamma), ptr(ln_beta), ln_gamma.stride(0) if ln_gamma.dim() == 2 else 0,
-                         float(ln_eps), ptr(y), ptr(mean), ptr(rstd), dtype_code(A), stream())
-    if st == _lib.CMX_ERR_ARG:
+    if refusable("cmx_gemm_ln", (CMX_ERR_ARG,), A, A2, B, C, bias, residual, rscale, G, M, N, Kd, K1, lda, lda2, ldb,
+                 C.stride(1), sA, sA2, sB, C.stride(0), sbias, int(rows_per_sample), ACT[act], ln_gamma, ln_beta,
+                 ln_gamma.stride(0) if ln_gamma.dim() == 2 else 0, float(ln_eps), y, mean, rstd,
+                 dtype_code(A)) is REFUSED:
         return None
-    if st != 0:
-        raise _lib.CMXError(f"cmx_gemm_ln failed ({st}): {_lib.last_error()}")
     return y, mean, rstd
 
 
@@ -244,14 +277,10 @@ def gemm_ln_bwd(dz, W, x, gamma, mean, rstd, dres=None, dy2=None, sscale=None, r
         return None
     dx = torch.empty_like(x)
     part = torch.empty(G, (M + 63) // 64, 2 * N, dtype=torch.float32, device=x.device)
-    st = _lib.try_call("cmx_gemm_ln_bwd", ptr(dz), ptr(W), ptr(dx), G, M, N, Kd, dz.stride(1), ldb, x.stride(1), dz.stride(0),
-                                  sB, x.stride(0), ptr(x), ptr(gamma), gamma.stride(0) if gamma.dim() == 2 else 0,
-                                  ptr(mean), ptr(rstd), ptr(dres), ptr(dy2), ptr(sscale), int(rows_per_sample), ptr(dxs),
-                                  ptr(part), dtype_code(dz), stream())
-    if st == _lib.CMX_ERR_ARG:
+    if refusable("cmx_gemm_ln_bwd", (CMX_ERR_ARG,), dz, W, dx, G, M, N, Kd, dz.stride(1), ldb, x.stride(1),
+                 dz.stride(0), sB, x.stride(0), x, gamma, gamma.stride(0) if gamma.dim() == 2 else 0, mean, rstd, dres,
+                 dy2, sscale, int(rows_per_sample), dxs, part, dtype_code(dz)) is REFUSED:
         return None
-    if st != 0:
-        raise _lib.CMXError(f"cmx_gemm_ln_bwd failed ({st}): {_lib.last_error()}")
     return dx, part
 
 
@@ -268,16 +297,20 @@ def conv_patch_dgrad_ln_bwd(dy, W, geom, x, gamma, mean, rstd, dres=None, dy2=No
     dx = torch.empty_like(x)
     nb = (NIg * Ho * Wo + 63) // 64 * R * R
     part = torch.empty(G, nb, 2 * C, dtype=torch.float32, device=x.device)
-    st = _lib.try_call("cmx_conv_patch_dgrad_ln_bwd", ptr(dy), ptr(W), ptr(dx), G, NIg, H, Wd, C, R, Ho, Wo, W.shape[1],
-                                              dy.stride(0), W.stride(0), NIg * H * Wd * C, ptr(x), ptr(gamma),
-                                              gamma.stride(0) if gamma.dim() == 2 else 0, ptr(mean), ptr(rstd),
-                                              ptr(dres), ptr(dy2), ptr(sscale), int(rows_per_sample), ptr(dxs),
-                                              ptr(part), dtype_code(dy), stream())
-    if st == _lib.CMX_ERR_ARG or st == _lib.CMX_ERR_SHAPE:
+    if refusable("cmx_conv_patch_dgrad_ln_bwd", (CMX_ERR_ARG, CMX_ERR_SHAPE), dy, W, dx, G, NIg, H, Wd, C, R, Ho, Wo,
+                 W.shape[1], dy.stride(0), W.stride(0), NIg * H * Wd * C, x, gamma,
+                 gamma.stride(0) if gamma.dim() == 2 else 0, mean, rstd, dres, dy2, sscale, int(rows_per_sample), dxs,
+                 part, dtype_code(dy)) is REFUSED:
         return None
-    if st != 0:
-        raise _lib.CMXError(f"cmx_conv_patch_dgrad_ln_bwd failed ({st}): {_lib.last_error()}")
     return dx, part
+
+
+def conv_patch_dgrad(dy, W, dx, geom):
+    """dx (the caller's) = col2im(dy @ W) alone (cmx_conv_patch_dgrad); layouts, geom: conv_patch_dgrad_ln_bwd's."""
+    G, NIg, H, Wd, C, R, Ho, Wo = geom
+    call("cmx_conv_patch_dgrad", dy, W, dx, G, NIg, H, Wd, C, R, Ho, Wo, W.shape[1], dy.stride(0), W.stride(0),
+         NIg * H * Wd * C, dtype_code(dy))
+    return dx
 
 
 _PLAN_BYTES = query("cmx_gemm_plan_size")
@@ -296,7 +329,7 @@ def gemm_multi(plans) -> None:
     buf = (ctypes.c_uint8 * (_PLAN_BYTES * n))()
     for i, p in enumerate(plans):
         ctypes.memmove(ctypes.addressof(buf) + i * _PLAN_BYTES, p.rec, _PLAN_BYTES)
-    call("cmx_gemm_multi", ctypes.addressof(buf), n, stream())
+    call("cmx_gemm_multi", ctypes.addressof(buf), n)
 
 
 def gemm_h2(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, out_mode: int = 0, splitk: int = 0) -> torch.Tensor:
@@ -320,9 +353,8 @@ def gemm_h2(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, out_mode: int = 0
     if splitk <= 0:
         splitk = query("cmx_gemm_splitk", G, M, N, K, 0, dtype_code(A))
     ws = _ws(query("cmx_gemm_workspace", G, M, N, splitk), A.device) if splitk > 1 else None
-    call("cmx_gemm_h2", ptr(A), ptr(B), ptr(C), ptr(ws), G, gh, M, N, K, lda, ldb, C.stride(2), A.stride(0),
-         A.stride(1), B.stride(0), B.stride(1), C.stride(0), C.stride(1), tA, tB, int(out_mode), int(splitk),
-         dtype_code(A), stream())
+    call("cmx_gemm_h2", A, B, C, ws, G, gh, M, N, K, lda, ldb, C.stride(2), A.stride(0), A.stride(1), B.stride(0),
+         B.stride(1), C.stride(0), C.stride(1), tA, tB, int(out_mode), int(splitk), dtype_code(A))
     return C
 
 
@@ -338,7 +370,7 @@ def sra_plan(Bt, N, Nk, heads, D, dtype, aligned=True) -> SraPlan:
     dK / dV kernel; dkv_direct: it stores dK / dV itself (no fp32 slabs, no reduce launch); dq_seq: the
     short-sequence dQ form; cus: the CU count used.  aligned: every row on 16 B (False: none; an int is
     passed through, bit 0 = q, k, v, o, dO, dq and bit 1 = dK / dV)."""
-    code = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[dtype]
+    code = _lib.DTYPE_CODES[dtype]
     out = (ctypes.c_int32 * 8)()
     call("cmx_sra_plan", ctypes.addressof(out), 8, Bt, N, Nk, heads, D, code, 3 if aligned is True else int(aligned))
     f = list(out)
@@ -350,8 +382,7 @@ def sra_attn_fwd(q, k, v, Bt, N, Nk, heads, D, scale, qs, kvs, save_lse=True):
     projection (k = kv[..., :C], v = kv[..., C:]) with row stride kvs."""
     o = torch.empty(Bt, N, heads * D, dtype=q.dtype, device=q.device)
     lse = torch.empty(Bt, heads, N, dtype=torch.float32, device=q.device) if save_lse else None
-    call("cmx_sra_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), Bt, N, Nk, heads, D, qs, kvs,
-         heads * D, float(scale), dtype_code(q), stream())
+    call("cmx_sra_attn_fwd", q, k, v, o, lse, Bt, N, Nk, heads, D, qs, kvs, heads * D, float(scale), dtype_code(q))
     return o, lse
 
 
@@ -362,7 +393,80 @@ def sra_attn_bwd(q, k, v, o, dout, lse, Bt, N, Nk, heads, D, scale, qs, kvs, dkv
     if dkv is None:
         dkv = torch.empty(Bt, Nk, 2 * C, dtype=q.dtype, device=q.device)
     ws = _ws(query("cmx_sra_attn_bwd_workspace", Bt, N, Nk, heads, D), q.device)
-    call("cmx_sra_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(dout), ptr(lse), ptr(dq),
-         ptr(dkv), dkv.data_ptr() + C * dkv.element_size(), ptr(ws), Bt, N, Nk, heads, D, qs, kvs, C,
-         C, C, 2 * C, float(scale), dtype_code(q), stream())
+    call("cmx_sra_attn_bwd", q, k, v, o, dout, lse, dq, dkv, dkv[..., C:], ws, Bt, N, Nk, heads, D, qs, kvs, C, C, C,
+         2 * C, float(scale), dtype_code(q))
     return dq, dkv
+
+
+# ------------------------------------------------------------------------------ conv (im2col, stage-1 direct)
+def im2col_nhwc(x, cols, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo):
+    """cols (G, NI/G*Ho*Wo, Kp), the caller's, = the im2col columns of x NHWC (NI, H, Wd, C) (cmx_im2col_nhwc)."""
+    call("cmx_im2col_nhwc", x, cols, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, cols.shape[-1], dtype_code(cols))
+    return cols
+
+
+def pe1_conv_fwd(img0, img1, W, b, geom, ln=None):
+    """y (G, Bg*Ho*Wo, N), W's dtype = the stage-1 conv straight from the fp32 NCHW batches img0 / img1 (one launch,
+    cmx_pe1_conv_fwd); geom = (G, Bg, C, H, Wd, KH, KW, stride, pad, Ho, Wo); ln = (gamma, beta, eps): also the
+    LayerNorm of y's rows, in the same epilogue, and (y, LN(y), mean, rstd) is returned."""
+    G, Bg, Ho, Wo = *geom[:2], *geom[-2:]
+    y = torch.empty(G, Bg * Ho * Wo, W.shape[1], dtype=W.dtype, device=W.device)
+    gamma, beta, eps = ln if ln is not None else (None, None, 0.0)
+    out = torch.empty_like(y) if ln is not None else None
+    mean = torch.empty(G * Bg * Ho * Wo, dtype=torch.float32, device=W.device) if ln is not None else None
+    rstd = torch.empty_like(mean) if ln is not None else None
+    call("cmx_pe1_conv_fwd", img0, img1, W, b, y, *geom, W.shape[1], W.shape[-1], W.stride(0), b.stride(0), y.stride(0),
+         gamma, beta, out, mean, rstd, gamma.stride(0) if ln is not None else 0, float(eps), dtype_code(W))
+    return y if ln is None else (y, out, mean, rstd)
+
+
+def pe1_conv_wgrad(dy, img0, img1, geom, N, Kp):
+    """The stage-1 conv's weight and bias gradient as per-workgroup partial slabs (G, nblk, N, Kp + 1) =
+    [dW | db] fp32 for the caller to reduce (cmx_pe1_conv_wgrad); geom as pe1_conv_fwd's."""
+    nblk = query("cmx_pe1_conv_wgrad_nblk", geom[1], *geom[-2:])
+    ws = torch.empty(geom[0], nblk, N, Kp + 1, dtype=torch.float32, device=dy.device)
+    call("cmx_pe1_conv_wgrad", dy, img0, img1, ws, *geom, N, Kp, dy.stride(0), dtype_code(dy))
+    return ws
+
+
+# ------------------------------------------------------------------------------ FRM pooling, BatchNorm scratch
+def frm_pool_fwd(x, tk):
+    """avg || max pooling of x (2, B, N, C) over N (cmx_frm_pool_fwd): pooled (B, 4C) fp32, argmax (B, 2C) int32;
+    tk: the call site's arrival counters (functions.pool_tickets)."""
+    _, B, N, C = x.shape
+    pooled = torch.empty(B, 4 * C, dtype=torch.float32, device=x.device)
+    argmax = torch.empty(B, 2 * C, dtype=torch.int32, device=x.device)
+    ws = _ws(query("cmx_frm_pool_workspace", B, N, C), x.device)
+    call("cmx_frm_pool_fwd", x, pooled, argmax, ws, tk, B, N, C, dtype_code(x))
+    return pooled, argmax
+
+
+def frm_pool_bwd(dpooled_part, argmax, dx):
+    """dx (2, B, N, C) += the pooling backward of dpooled, given as small_linear_bwd's (nslice, B, 4C) slices."""
+    _, B, N, C = dx.shape
+    call("cmx_frm_pool_bwd", dpooled_part, dpooled_part.shape[0], B * 4 * C, argmax, dx, B, N, C, dtype_code(dx))
+
+
+def bn_scratch(M, C, device):
+    """(sums (2, C), workspace) fp64 of the BatchNorm statistics / backward-reduce kernels."""
+    sums = torch.empty(2, C, dtype=torch.float64, device=device)
+    return sums, torch.empty(max(1, query("cmx_bn_workspace", M, C) // 8), dtype=torch.float64, device=device)
+
+
+# ------------------------------------------------------------------------------ decoder
+def bilinear_adjoint_1d(src, out, P, Lo, Li, Q, sp, so, a1=None, a2=None):
+    """One separable pass of the bilinear adjoint, Lo -> Li samples along one axis, into out (the caller's), in the
+    tensors' dtypes (cmx_bilinear_adjoint_1d); a1 / a2 (1-element fp32, optional): scaled by a1[0] / a2[0]."""
+    call("cmx_bilinear_adjoint_1d", src, out, P, Lo, Li, Q, sp, so, a1, a2, 1.0, dtype_code(src), dtype_code(out))
+    return out
+
+
+def decoder_fuse_fwd(e1, Wc1, bias, zs, H1, W1, hw):
+    """Z (B*N1, E) = e1 Wc1^T + bias + up(zs[0]) + up(zs[1]) + up(zs[2]) (cmx_decoder_fuse_fwd: the upsample of the
+    c4, c3, c2 products, grids hw[2], hw[1], hw[0], in the c1 GEMM's epilogue); e1 (B, N1, K) contiguous, Wc1 (E, K)."""
+    B, N1, Kd = e1.shape
+    E = Wc1.shape[0]
+    Z = torch.empty(B * N1, E, dtype=e1.dtype, device=e1.device)
+    call("cmx_decoder_fuse_fwd", e1, Wc1, Z, bias, zs[0], zs[1], zs[2], B, H1, W1, *hw[2], *hw[1], *hw[0], E, Kd, Kd,
+         Wc1.stride(0), dtype_code(e1))
+    return Z

@@ -298,8 +298,8 @@ class EncoderDecoder(nn.Module):
         dp = torch.empty_like(keep)
         d2 = torch.empty(B, E, device=device) if p > 0 else None
         nbt = getattr(self, "_nbt", None)
-        K.call("cmx_step_masks", K.ptr(keep), keep.numel(), K.ptr(dp), B * E if d2 is not None else 0, float(p),
-               K.ptr(d2), st[0], K.ptr(st[1]), K.ptr(nbt), nbt.numel() if nbt is not None else 0, K.stream())
+        K.call("cmx_step_masks", keep, keep.numel(), dp, B * E if d2 is not None else 0, float(p), d2, st[0], st[1], nbt,
+               nbt.numel() if nbt is not None else 0)
         self._nbt_bumped = True
         return dp, d2
 

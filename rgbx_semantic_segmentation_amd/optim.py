@@ -21,8 +21,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
-from ._lib import call, ptr, query, stream
+from ._lib import call, query
 
 class _Group(dict):
     """param_group dict whose 'lr' writes through to the device scalar."""
@@ -90,15 +89,14 @@ class FusedAdamW:
             # GradScaler.step: skip the update if any (scaled) gradient is inf / nan, else unscale
             # the frozen slots (IFRM lambdas, in no param group) are not checked, as
             # GradScaler.unscale_ only checks the optimizer's parameters
-            call("cmx_grad_nonfinite", ptr(s.grad), s.numel, ptr(s.decay64), ptr(scaler.found_inf), stream())
-            call("cmx_adamw_step_scaled", ptr(s.flat), ptr(s.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                 ptr(s.shadow), s.shadow_code, ptr(s.decay64), s.numel, ptr(self.lr_t), ptr(self.step_t), self.betas[0],
-                 self.betas[1], self.eps, self.weight_decay, gscale, ptr(scaler.scale_t), ptr(scaler.found_inf),
-                 ptr(self.tickets), stream())
+            call("cmx_grad_nonfinite", s.grad, s.numel, s.decay64, scaler.found_inf)
+            call("cmx_adamw_step_scaled", s.flat, s.grad, self.exp_avg, self.exp_avg_sq, s.shadow, s.shadow_code,
+                 s.decay64, s.numel, self.lr_t, self.step_t, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                 gscale, scaler.scale_t, scaler.found_inf, self.tickets)
             return None
-        call("cmx_adamw_step", ptr(s.flat), ptr(s.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(s.shadow),
-             s.shadow_code, ptr(s.decay64), s.numel, ptr(self.lr_t), ptr(self.step_t), self.betas[0], self.betas[1], self.eps,
-             self.weight_decay, gscale, ptr(self.tickets), stream())
+        call("cmx_adamw_step", s.flat, s.grad, self.exp_avg, self.exp_avg_sq, s.shadow, s.shadow_code, s.decay64,
+             s.numel, self.lr_t, self.step_t, self.betas[0], self.betas[1], self.eps, self.weight_decay, gscale,
+             self.tickets)
         return None
 
     # ------------------------------------------------------------------ checkpoint format
@@ -193,11 +191,10 @@ class FusedSGD:
         loss_scale = found_inf = None
         if scaler is not None and scaler.enabled:
             # GradScaler.step, as in FusedAdamW.step: flag inf / nan, then unscale or skip in the kernel
-            call("cmx_grad_nonfinite", ptr(s.grad), s.numel, ptr(s.decay64), ptr(scaler.found_inf), stream())
+            call("cmx_grad_nonfinite", s.grad, s.numel, s.decay64, scaler.found_inf)
             loss_scale, found_inf = scaler.scale_t, scaler.found_inf
-        call("cmx_sgdm_step", ptr(s.flat), ptr(s.grad), ptr(self.momentum_buffer), ptr(s.shadow), s.shadow_code,
-             ptr(s.decay64), s.numel, ptr(self.lr_t), self.momentum, self.weight_decay, int(self.nesterov), gscale,
-             ptr(loss_scale), ptr(found_inf), 0, stream())
+        call("cmx_sgdm_step", s.flat, s.grad, self.momentum_buffer, s.shadow, s.shadow_code, s.decay64, s.numel,
+             self.lr_t, self.momentum, self.weight_decay, self.nesterov, gscale, loss_scale, found_inf, 0)
         return None
 
     # ------------------------------------------------------------------ checkpoint format
@@ -266,8 +263,8 @@ class GradScaler:
         if new_scale is not None:
             self.scale_t.fill_(float(new_scale))
             return
-        call("cmx_loss_scale_update", ptr(self.scale_t), ptr(self.tracker), ptr(self.found_inf), self.growth_factor,
-             self.backoff_factor, self.growth_interval, stream())
+        call("cmx_loss_scale_update", self.scale_t, self.tracker, self.found_inf, self.growth_factor,
+             self.backoff_factor, self.growth_interval)
 
     def get_scale(self) -> float:
         return float(self.scale_t.item()) if self.enabled else 1.0

@@ -329,7 +329,7 @@ def measure_dominant(model, batch, workload: str, iters: int = 20):
         for (G, M, Nr, K) in work:
             flops += 2.0 * G * M * Nr * K
             nbytes += 2.0 * G * (M + Nr) * K + 4.0 * G * M * Nr
-        launch = lambda: _lib.call("cmx_gemm_grouped", dev.data_ptr(), nr, bl, dcode, _lib.stream())
+        launch = lambda: _lib.call("cmx_gemm_grouped", dev, nr, bl, dcode)
         for _ in range(3):
             launch()
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

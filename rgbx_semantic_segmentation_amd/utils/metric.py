@@ -46,16 +46,16 @@ class ConfusionCounter:
         if gt.shape != (H, W):
             raise RuntimeError(f"hist_info_from_score: label shape {tuple(gt.shape)} != score {(H, W)}")
         score = score.contiguous()
-        _lib.call("cmx_seg_argmax_confusion", _lib.ptr(score), K, H * W, _lib.ptr(gt), _label_code(gt), self.n_cl,
-                  _lib.ptr(pred_out), _lib.ptr(self.hist), _lib.ptr(self.counts), _lib.stream())
+        _lib.call("cmx_seg_argmax_confusion", score, K, H * W, gt, _label_code(gt), self.n_cl, pred_out, self.hist,
+                  self.counts)
 
     def add_pred(self, pred: torch.Tensor, gt: torch.Tensor):
         pred = pred.to(device=self.hist.device, dtype=torch.int32).contiguous()
         gt = gt.to(self.hist.device).contiguous()
         if pred.shape != gt.shape:
             raise AssertionError("hist_info: pred and gt shapes differ")
-        _lib.call("cmx_seg_argmax_confusion", None, 0, pred.numel(), _lib.ptr(gt), _label_code(gt), self.n_cl,
-                  _lib.ptr(pred), _lib.ptr(self.hist), _lib.ptr(self.counts), _lib.stream())
+        _lib.call("cmx_seg_argmax_confusion", None, 0, pred.numel(), gt, _label_code(gt), self.n_cl, pred, self.hist,
+                  self.counts)
 
     def result(self):
         h = self.hist.cpu().numpy().reshape(self.n_cl, self.n_cl)
