@@ -98,3 +98,28 @@ template <> __device__ __forceinline__ bf16x8 zfrag<bf16>() {
 template <> __device__ __forceinline__ f16x8 zfrag<f16>() {
   return __builtin_bit_cast(f16x8, make_uint4(0, 0, 0, 0));
 }
+
+// 4 consecutive elements (16 B of fp32, 8 B of a 16-bit type)
+template <typename T>
+__device__ __forceinline__ void store4(T* p, const float* v) {
+  if constexpr (sizeof(T) == 4) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    uint32_t a = pack2<T>(v[0], v[1]);
+    uint32_t b = pack2<T>(v[2], v[3]);
+    *reinterpret_cast<uint2*>(p) = make_uint2(a, b);
+  }
+}
+
+// store the 32-row (d) x 32-col (lane) accumulator tile t, scaled by mul, into row `row_ptr` of this
+// lane (d contiguous: registers 4 k4 .. 4 k4 + 3 are d = 32 t + 8 k4 + 4 h + 0 .. 3)
+template <typename T>
+__device__ __forceinline__ void store_acc_row(T* row_ptr, const f32x16& acc, int t, int h, float mul) {
+#pragma unroll
+  for (int k4 = 0; k4 < 4; ++k4) {
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = acc[4 * k4 + u] * mul;
+    store4<T>(row_ptr + 32 * t + 8 * k4 + 4 * h, v);
+  }
+}

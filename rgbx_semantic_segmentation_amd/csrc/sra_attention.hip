@@ -24,7 +24,7 @@
 //          bit-reproducible).
 // MFMA FLOPs per (b, head): fwd 4*N*Nk*D, bwd 8*N*Nk*D (+ S recompute 2*N*Nk*D).
 #include "cmx_mfma.h"
-#include "sra_plan.h"
+#include "sra_args.h"
 
 namespace {
 
@@ -83,29 +83,6 @@ __device__ __forceinline__ typename MF<T>::frag perm_frag(const T* rowimg, const
   } else {
     constexpr int KS = Lds<T, D>::KS;
     return rowimg[accrow(s, h) * KS + 32 * t + r];
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void store4(T* p, const float* v) {
-  if constexpr (sizeof(T) == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    uint32_t a = pack2<T>(v[0], v[1]);
-    uint32_t b = pack2<T>(v[2], v[3]);
-    *reinterpret_cast<uint2*>(p) = make_uint2(a, b);
-  }
-}
-
-// store the 32-row (d) x 32-col (lane) accumulator tile t of row `row_ptr` (d contiguous)
-template <typename T>
-__device__ __forceinline__ void store_acc_row(T* row_ptr, const f32x16& acc, int t, int h, float mul) {
-#pragma unroll
-  for (int k4 = 0; k4 < 4; ++k4) {
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = acc[4 * k4 + u] * mul;
-    store4<T>(row_ptr + 32 * t + 8 * k4 + 4 * h, v);
   }
 }
 
@@ -427,33 +404,6 @@ int bwd_qc(int N, int nchunk) {
   return (qc + KT - 1) / KT * KT;
 }
 
-}  // namespace
-
-// sra_fast.hip: LDS-resident K/V kernels for bf16 / fp16, D = 64 (any Nk: keys stream through LDS
-// in 320-key chunks) and their short-sequence forms (Nk <= 320).  sra_plan_now is the launch
-// decision (sra_plan.h) under the live knobs; the launchers below take its fields.
-sraplan::SraPlan sra_plan_now(int Bt, int N, int Nk, int heads, int D, int dtype, int aligned);
-int sra_dkv_fast_chunks(int Bt, int N, int Nk, int heads);
-void sra_fwd_fast_launch(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
-                         int heads, long qs, long kvs, long os, float sl2, int qw, int nw, int dtype, hipStream_t s);
-void sra_dq_fast_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                        const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                        long os, long dos, long dqs, float sl2, float scale, int qw, int nw, int dtype,
-                        hipStream_t s);
-void sra_dkv_fast_launch(const void* q, const void* k, const void* v, const void* dout, const float* lse,
-                         const float* Dws, float* ws_dk, float* ws_dv, void* dk, void* dv, long dkvs, int Bt, int N,
-                         int Nk, int heads, long qs,
-                         long kvs, long dos, int nchunk, float sl2, float scale, int dtype, hipStream_t s);
-void sra_fwd_small_launch(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
-                          int heads, long qs, long kvs, long os, float sl2, int dtype, hipStream_t s);
-void sra_dq_small_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                         const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                         long os, long dos, long dqs, float sl2, float scale, int seq, int dtype, hipStream_t s);
-void sra_dkv_small_launch(const void* q, const void* k, const void* v, const void* dout, const float* lse,
-                          const float* Dws, void* dk, void* dv, long dkvs, int Bt, int N, int Nk, int heads, long qs,
-                          long kvs, long dos, float sl2, float scale, int dtype, hipStream_t s);
-
-namespace {
 // 16-B aligned starts and row strides of whole 16-B groups (`aligned` of plan_sra)
 bool rows16(const void* const* ptrs, int nptr, const long* strides, int nstr) {
   for (int i = 0; i < nptr; ++i)
@@ -462,6 +412,31 @@ bool rows16(const void* const* ptrs, int nptr, const long* strides, int nstr) {
     if (strides[i] % 8) return false;
   return true;
 }
+
+// the general kernels, launched from the problem struct
+template <typename T, int D>
+void general_fwd(const SraArgs& a) {
+  hipLaunchKernelGGL((sra_fwd_kernel<T, D>), dim3(cdiv(a.N, BQ), a.heads, a.Bt), dim3(256), 0, a.stream,
+                     (const T*)a.q, (const T*)a.k, (const T*)a.v, (T*)a.o, a.lse, a.N, a.Nk, a.heads, a.qs, a.kvs,
+                     a.os, a.sl2);
+}
+template <typename T, int D>
+void general_bwd(const SraArgs& a, int nc) {
+  hipLaunchKernelGGL((sra_bwd_dq_kernel<T, D>), dim3(cdiv(a.N, BQ), a.heads, a.Bt), dim3(256), 0, a.stream,
+                     (const T*)a.q, (const T*)a.k, (const T*)a.v, (const T*)a.o, (const T*)a.dout, a.lse, a.Dws,
+                     (T*)a.dq, a.N, a.Nk, a.heads, a.qs, a.kvs, a.os, a.dos, a.dqs, a.sl2, a.scale);
+  hipLaunchKernelGGL((sra_bwd_dkv_kernel<T, D>), dim3(cdiv(a.Nk, BK), a.heads, a.Bt * nc), dim3(256), 0, a.stream,
+                     (const T*)a.q, (const T*)a.k, (const T*)a.v, (const T*)a.dout, a.lse, a.Dws, a.ws_dk, a.ws_dv,
+                     a.Bt, a.N, a.Nk, a.heads, a.qs, a.kvs, a.dos, bwd_qc(a.N, nc), nc, a.sl2, a.scale);
+}
+// dK / dV = the sum of the nc slabs (general and fast dK / dV alike)
+template <typename T>
+void fold_slabs(const SraArgs& a, int nc) {
+  const long total = (long)a.Bt * a.heads * a.Nk * a.D;   // D % 4 == 0: 4-wide groups never straddle a row
+  hipLaunchKernelGGL((sra_dkv_reduce_kernel<T>), dim3(cdiv(total / 4, 64)), dim3(256), 0, a.stream, a.ws_dk, a.ws_dv,
+                     (T*)a.dk, (T*)a.dv, a.Bt, a.Nk, a.heads, a.D, a.dkvs, nc);
+}
+
 }  // namespace
 
 #define SRA_D_DISPATCH(D, ...)                                              \
@@ -479,23 +454,16 @@ int cmx_sra_attn_fwd(const void* q, const void* k, const void* v, void* o, float
                      hipStream_t s) {
   CMX_REQUIRE(Bt > 0 && N > 0 && Nk > 0 && heads > 0, CMX_ERR_SHAPE, "sra_fwd: bad shape");
   CMX_REQUIRE(qs % 8 == 0 && kvs % 8 == 0 && os % 8 == 0, CMX_ERR_SHAPE, "sra_fwd: strides %% 8");
-  const float sl2 = scale * 1.4426950408889634f;
+  SraArgs a = {};
+  a.q = q, a.k = k, a.v = v, a.o = o, a.lse = lse;
+  a.Bt = Bt, a.N = N, a.Nk = Nk, a.heads = heads, a.D = D;
+  a.qs = qs, a.kvs = kvs, a.os = os;
+  a.sl2 = scale * 1.4426950408889634f, a.scale = scale, a.dtype = dtype, a.stream = s;
   const void* ptrs[] = {q, k, v, o};
   const long strides[] = {qs, kvs, os};
   const sraplan::SraPlan plan = sra_plan_now(Bt, N, Nk, heads, D, dtype, rows16(ptrs, 4, strides, 3) ? 1 : 0);
-  if (plan.fwd == sraplan::SRA_SMALL) {
-    sra_fwd_small_launch(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, dtype, s);
-    return cmx_check_launch("sra_fwd");
-  }
-  if (plan.fwd == sraplan::SRA_FAST) {
-    sra_fwd_fast_launch(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, plan.qw, plan.nw, dtype, s);
-    return cmx_check_launch("sra_fwd");
-  }
-  const dim3 grid(cdiv(N, BQ), heads, Bt);
-  SRA_D_DISPATCH(D, CMX_DISPATCH(dtype, T, {
-    hipLaunchKernelGGL((sra_fwd_kernel<T, DD>), grid, dim3(256), 0, s, (const T*)q, (const T*)k,
-                       (const T*)v, (T*)o, lse, N, Nk, heads, qs, kvs, os, sl2);
-  }));
+  if (plan.fwd != sraplan::SRA_GENERAL) sra_lds_fwd(a, plan);
+  else SRA_D_DISPATCH(D, CMX_DISPATCH(dtype, T, general_fwd<T, DD>(a)));
   return cmx_check_launch("sra_fwd");
 }
 
@@ -514,47 +482,26 @@ int cmx_sra_attn_bwd(const void* q, const void* k, const void* v, const void* o,
   CMX_REQUIRE(Bt > 0 && N > 0 && Nk > 0 && heads > 0, CMX_ERR_SHAPE, "sra_bwd: bad shape");
   CMX_REQUIRE(qs % 8 == 0 && kvs % 8 == 0 && os % 8 == 0 && dos % 8 == 0 && dqs % 8 == 0 && dkvs % 8 == 0,
               CMX_ERR_SHAPE, "sra_bwd: strides %% 8");
-  const float sl2 = scale * 1.4426950408889634f;
   const void* ptrs[] = {q, k, v, o, dout, dq};
   const long strides[] = {qs, kvs, os, dos, dqs};
   const void* gptrs[] = {dk, dv};
   const int aligned = (rows16(ptrs, 6, strides, 5) ? 1 : 0) | (rows16(gptrs, 2, &dkvs, 1) ? 2 : 0);
   const sraplan::SraPlan plan = sra_plan_now(Bt, N, Nk, heads, D, dtype, aligned);
-  if (plan.bwd == sraplan::SRA_SMALL) {
-    // short sequences: keys split over waves (dQ), query tiles over waves (dK / dV), no slabs
-    float* Dws = workspace;
-    sra_dq_small_launch(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale,
-                        plan.dq_seq, dtype, s);
-    sra_dkv_small_launch(q, k, v, dout, lse, Dws, dk, dv, dkvs, Bt, N, Nk, heads, qs, kvs, dos, sl2, scale, dtype, s);
-    return cmx_check_launch("sra_bwd");
-  }
-  // fast path for any Nk: dQ streams K / V in LDS-sized chunks, dK / dV splits keys over workgroups
-  const bool fast = plan.bwd == sraplan::SRA_FAST;
   const int nc = plan.dkv_chunks;
-  const int qc = bwd_qc(N, nc);
-  float* Dws = workspace;
-  float* ws_dk = Dws + (size_t)Bt * heads * N;
-  float* ws_dv = ws_dk + (size_t)nc * Bt * heads * Nk * D;
-  SRA_D_DISPATCH(D, CMX_DISPATCH(dtype, T, {
-    if (fast)
-      sra_dq_fast_launch(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, plan.qw,
-                         plan.nw, dtype, s);
-    else
-      hipLaunchKernelGGL((sra_bwd_dq_kernel<T, DD>), dim3(cdiv(N, BQ), heads, Bt), dim3(256), 0, s,
-                         (const T*)q, (const T*)k, (const T*)v, (const T*)o, (const T*)dout, lse, Dws,
-                         (T*)dq, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale);
-    if (fast)
-      sra_dkv_fast_launch(q, k, v, dout, lse, Dws, ws_dk, ws_dv, dk, dv, dkvs, Bt, N, Nk, heads, qs, kvs, dos, nc, sl2,
-                          scale, dtype, s);
-    else
-      hipLaunchKernelGGL((sra_bwd_dkv_kernel<T, DD>), dim3(cdiv(Nk, BK), heads, Bt * nc), dim3(256), 0, s,
-                         (const T*)q, (const T*)k, (const T*)v, (const T*)dout, lse, Dws, ws_dk, ws_dv, Bt,
-                         N, Nk, heads, qs, kvs, dos, qc, nc, sl2, scale);
-    const long total = (long)Bt * heads * Nk * D;     // D % 4 == 0: 4-wide groups never straddle a row
-    if (!plan.dkv_direct)                             // one chunk: the fast kernel wrote dK / dV
-    hipLaunchKernelGGL((sra_dkv_reduce_kernel<T>), dim3(cdiv(total / 4, 64)), dim3(256), 0, s, ws_dk, ws_dv, (T*)dk,
-                       (T*)dv, Bt, Nk, heads, D, dkvs, nc);
-  }));
+  SraArgs a = {};
+  a.q = q, a.k = k, a.v = v, a.o = const_cast<void*>(o), a.dout = dout, a.lse = const_cast<float*>(lse);
+  a.dq = dq, a.dk = dk, a.dv = dv;
+  a.Dws = workspace;                              // then the two slab sets (unused when dkv_direct)
+  a.ws_dk = a.Dws + (size_t)Bt * heads * N;
+  a.ws_dv = a.ws_dk + (size_t)nc * Bt * heads * Nk * D;
+  a.Bt = Bt, a.N = N, a.Nk = Nk, a.heads = heads, a.D = D;
+  a.qs = qs, a.kvs = kvs, a.os = os, a.dos = dos, a.dqs = dqs, a.dkvs = dkvs;
+  a.sl2 = scale * 1.4426950408889634f, a.scale = scale, a.dtype = dtype, a.stream = s;
+  // small: keys split over waves (dQ), query tiles over waves (dK / dV), no slabs.  fast, any Nk: dQ
+  // streams K / V in LDS-sized chunks, dK / dV splits keys over workgroups
+  if (plan.bwd != sraplan::SRA_GENERAL) sra_lds_bwd(a, plan);
+  else SRA_D_DISPATCH(D, CMX_DISPATCH(dtype, T, general_bwd<T, DD>(a, nc)));
+  if (!plan.dkv_direct) CMX_DISPATCH(dtype, T, fold_slabs<T>(a, nc));   // direct: the dK / dV kernel wrote them
   return cmx_check_launch("sra_bwd");
 }
 

@@ -18,9 +18,17 @@
 //    dQ^T = K^T dS^T, straight from the accumulator with no LDS round trip.
 // Queries stay on the MFMA lane (S^T tiles), so the online softmax is per lane plus one
 // cross-half shuffle; each wave owns QW 32-query sub-tiles for MFMA/VALU overlap.
-#include "cmx_mfma.h"
+//
+// Shared __forceinline__ blocks (first section; the accumulator store is cmx_mfma.h's): the score mask
+// and row max of the forwards, and for the short-sequence kernels the K / V staging, the dQ row
+// prologue, the dQ dS tile and the output sum.  The three fast kernels keep their own offset tables,
+// tile driver, staging, row prologues and dS block, both forwards their exponent loop and both
+// dK / dV kernels their P / dS block: each of those, moved into a helper, changed a fast kernel's
+// register allocation (sra_fwd_fast measured slower for it) or, in the dK / dV kernels, which product
+// of S sl2 - lse log2 e the compiler fuses, and with it result bits (profiles/sra_dedupe/README.md).
 #include "cmx_dma.h"
-#include "sra_plan.h"
+#include "cmx_mfma.h"
+#include "sra_args.h"
 #include <stdlib.h>
 
 namespace {
@@ -52,6 +60,15 @@ __device__ __forceinline__ void stage_rows(const E* __restrict__ g, long ld, int
     const int off = row < Nk ? (int)(((long)row * ld + c * 8) * 2) : OOB;
     dma16(rs, lds_addr(img + j * 1024), off);
   }
+}
+
+// keys [r0, r0 + n) of (b, head): K -> image Ki, V -> image Vi (nkp rows each, zero past n), issued by
+// `nwaves` waves (this one is `wave`); the caller waits
+template <typename E>
+__device__ __forceinline__ void stage_kv(const E* k, const E* v, int b, int head, int Nk, long kvs, int r0, int n,
+                                         int nkp, char* Ki, char* Vi, int wave, int lane, int nwaves) {
+  stage_rows(k + ((long)b * Nk + r0) * kvs + head * HD, kvs, n, nkp, Ki, wave, lane, nwaves);
+  stage_rows(v + ((long)b * Nk + r0) * kvs + head * HD, kvs, n, nkp, Vi, wave, lane, nwaves);
 }
 
 // A operand, k = d contiguous: row rb + (lane & 31), d in [16 s + 8 h, +8)
@@ -107,13 +124,75 @@ __device__ __forceinline__ frag8<E> frag_t_o(const char* p0, const char* p1) {
 
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-template <typename E>
-__device__ __forceinline__ void store_rows(E* row_ptr, const f32x16& acc, int t, int h, float mul) {
+// ---- the forwards: mask and row max on the raw S^T scores of one 64-key tile (query on the lane)
+// keys >= nk of the tile at key t0 score -inf
+__device__ __forceinline__ void mask_scores(f32x16 (&sa)[2], int t0, int nk, int h) {
 #pragma unroll
-  for (int k4 = 0; k4 < 4; ++k4) {
-    const uint32_t a = pack2<E>(acc[4 * k4] * mul, acc[4 * k4 + 1] * mul);
-    const uint32_t b = pack2<E>(acc[4 * k4 + 2] * mul, acc[4 * k4 + 3] * mul);
-    *reinterpret_cast<uint2*>(row_ptr + 32 * t + 8 * k4 + 4 * h) = make_uint2(a, b);
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (t0 + 32 * ks + accrow(i, h) >= nk) sa[ks][i] = -INFINITY;
+}
+// the row max in log2 units: max on the raw scores (the scale is positive)
+__device__ __forceinline__ float score_max(const f32x16 (&sa)[2], float sl2) {
+  float mt = -INFINITY;
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mt = fmaxf(mt, sa[ks][i]);
+  return fmaxf(mt, xor_lane<32>(mt)) * sl2;
+}
+
+// ---- dQ, short sequences: the row prologue.  Query row qi of (b, head) on the lane (half h supplies its 8 elements of
+// every k-step): the Q and dO fragments (zero past N), Dq = rowsum(dO . O) as one sum chained through
+// the row, lse in log2 units; the `writer` lanes store Dq to Dws
+template <typename E>
+__device__ __forceinline__ void sra_dq_row(const E* q, const E* o, const E* dout, const float* lse, float* Dws, int b,
+                                           int head, int heads, int N, int qi, long qs, long os, long dos, int h,
+                                           bool writer, frag8<E> (&qf)[4], frag8<E> (&df)[4], float& Dq, float& lse2) {
+  const bool live = qi < N;
+  const E* qrow = q + ((long)b * N + qi) * qs + head * HD;
+  const E* orow = o + ((long)b * N + qi) * os + head * HD;
+  const E* drow = dout + ((long)b * N + qi) * dos + head * HD;
+  float dot = 0.f;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    if (live) {
+      qf[s] = frag_bits<E>(*reinterpret_cast<const uint4*>(qrow + 16 * s + 8 * h));
+      df[s] = frag_bits<E>(*reinterpret_cast<const uint4*>(drow + 16 * s + 8 * h));
+      float x[8], y[8];
+      load_vec<E>(drow + 16 * s + 8 * h, x);
+      load_vec<E>(orow + 16 * s + 8 * h, y);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dot += x[j] * y[j];
+    } else {
+      qf[s] = df[s] = zfrag<E>();
+    }
+  }
+  dot += xor_lane<32>(dot);
+  Dq = dot;
+  const long sidx = ((long)b * heads + head) * N + qi;
+  lse2 = live ? lse[sidx] * 1.4426950408889634f : 0.f;
+  if (live && writer) Dws[sidx] = dot;
+}
+
+// ---- dQ, short sequences: dS^T of one 32-key x 32-query tile (query on the lane, keys kb + accrow(i, h)):
+// p = exp2(S sl2 - lse2), p = 0 at keys >= nk, dS = p (dP - Dq) -> ds (which may be sa: each pair is
+// read before it is written).  `ragged` (wave-uniform): the tile holds keys >= nk, the last wave's only
+__device__ __forceinline__ void dq_ds_tile(const f32x16& sa, const f32x16& dp, f32x16& ds, float sl2, float lse2,
+                                           float Dq, int kb, int nk, int h, bool ragged) {
+  const f2 sl2v = {sl2, sl2}, nl = {-lse2, -lse2}, nD = {-Dq, -Dq};
+#pragma unroll
+  for (int i = 0; i < 16; i += 2) {
+    const f2 a = f2{sa[i], sa[i + 1]} * sl2v + nl;
+    f2 p = {fexp2(a.x), fexp2(a.y)};
+    if (ragged) {
+      if (kb + accrow(i, h) >= nk) p.x = 0.f;
+      if (kb + accrow(i + 1, h) >= nk) p.y = 0.f;
+    }
+    const f2 d = p * (f2{dp[i], dp[i + 1]} + nD);
+    ds[i] = d.x;
+    ds[i + 1] = d.y;
   }
 }
 
@@ -187,20 +266,8 @@ __global__ __launch_bounds__(64 * NW) void sra_fwd_fast(const E* __restrict__ q,
     }
 #pragma unroll
     for (int u = 0; u < QW; ++u) {
-      if constexpr (MASK) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int i = 0; i < 16; ++i)
-            if (t0 + 32 * ks + accrow(i, h) >= nc) sa[u][ks][i] = -INFINITY;
-      }
-      float mt = -INFINITY;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mt = fmaxf(mt, sa[u][ks][i]);
-      // max on the raw scores (the scale is positive), exponent as one packed FMA per 2 scores
-      mt = fmaxf(mt, xor_lane<32>(mt)) * sl2;
+      if constexpr (MASK) mask_scores(sa[u], t0, nc, h);
+      const float mt = score_max(sa[u], sl2);
       const float mn = fmaxf(m[u], mt);
       const float alpha = fexp2(m[u] - mn);
       const f2 sl2v = {sl2, sl2}, nmn = {-mn, -mn};
@@ -254,8 +321,8 @@ __global__ __launch_bounds__(64 * NW) void sra_fwd_fast(const E* __restrict__ q,
     if (qi >= N) continue;
     const float inv = 1.f / l[u];
     E* ob = o + ((long)b * N + qi) * os + head * HD;
-    store_rows(ob, acc[u][0], 0, h, inv);
-    store_rows(ob, acc[u][1], 1, h, inv);
+    store_acc_row(ob, acc[u][0], 0, h, inv);
+    store_acc_row(ob, acc[u][1], 1, h, inv);
     if (h == 0 && lse) lse[((long)b * heads + head) * N + qi] = (m[u] + __log2f(l[u])) * 0.69314718055994531f;
   }
 }
@@ -388,8 +455,8 @@ __global__ __launch_bounds__(64 * NW) void sra_dq_fast(const E* __restrict__ q, 
     const int qi = q0 + 32 * u + r;
     if (qi >= N) continue;
     E* out = dq + ((long)b * N + qi) * dqs + head * HD;
-    store_rows(out, acc[u][0], 0, h, scale);
-    store_rows(out, acc[u][1], 1, h, scale);
+    store_acc_row(out, acc[u][0], 0, h, scale);
+    store_acc_row(out, acc[u][1], 1, h, scale);
   }
 }
 
@@ -608,6 +675,18 @@ __device__ __forceinline__ void sum_store8(const char* smem, int nw, long rs, in
   store_vec<E>(out, a);
 }
 
+// the end of the short-sequence forward and dQ: the waves' [rows][64] tiles (put_tile) summed into
+// query rows [q0, q0 + rows) of (b, head) of `out` (row stride ld), rows past N left alone
+template <typename E>
+__device__ __forceinline__ void sum_store_queries(const char* smem, int nw, int rows, E* out, int b, int head, int N,
+                                                  int q0, long ld) {
+  __syncthreads();
+  for (int it = threadIdx.x; it < rows * 8; it += blockDim.x) {
+    const int row = it >> 3, dg = it & 7, qi = q0 + row;
+    if (qi < N) sum_store8<E>(smem, nw, SREG, row, dg, 1.f, out + ((long)b * N + qi) * ld + head * HD + 8 * dg);
+  }
+}
+
 // forward: workgroup = 64 queries of one (b, head); wave w = key tile w
 template <typename E>
 __global__ __launch_bounds__(64 * SKT) void sra_fwd_small(const E* __restrict__ q, const E* __restrict__ k,
@@ -621,8 +700,7 @@ __global__ __launch_bounds__(64 * SKT) void sra_fwd_small(const E* __restrict__ 
   char* Ki = smem + wave * SREG;
   char* Vi = Ki + KTILE * ROWB;
   const int t0 = wave * KTILE, nkw = min(KTILE, Nk - t0);
-  stage_rows<E>(k + ((long)b * Nk + t0) * kvs + head * HD, kvs, nkw, KTILE, Ki, 0, lane, 1);
-  stage_rows<E>(v + ((long)b * Nk + t0) * kvs + head * HD, kvs, nkw, KTILE, Vi, 0, lane, 1);
+  stage_kv(k, v, b, head, Nk, kvs, t0, nkw, KTILE, Ki, Vi, 0, lane, 1);
   const E* qb = q + (long)b * N * qs + head * HD;
   frag8<E> qf[2][4];
 #pragma unroll
@@ -649,21 +727,11 @@ __global__ __launch_bounds__(64 * SKT) void sra_fwd_small(const E* __restrict__ 
   float m[2], l[2];
   if (nkw < KTILE) {                             // only the last wave's tile is ragged
 #pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if (32 * ks + accrow(i, h) >= nkw) sa[u][ks][i] = -INFINITY;
+    for (int u = 0; u < 2; ++u) mask_scores(sa[u], 0, nkw, h);
   }
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    float mt = -INFINITY;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mt = fmaxf(mt, sa[u][ks][i]);
-    mt = fmaxf(mt, xor_lane<32>(mt)) * sl2;
+    const float mt = score_max(sa[u], sl2);
     const f2 sl2v = {sl2, sl2}, nmt = {-mt, -mt};
     f2 rs2 = {0.f, 0.f};
 #pragma unroll
@@ -726,11 +794,7 @@ __global__ __launch_bounds__(64 * SKT) void sra_fwd_small(const E* __restrict__ 
     if (wave == 0 && h == 0 && lse && qi < N)
       lse[((long)b * heads + head) * N + qi] = (M[u] + __log2f(L[u])) * 0.69314718055994531f;
   }
-  __syncthreads();
-  for (int it = threadIdx.x; it < 64 * 8; it += blockDim.x) {
-    const int row = it >> 3, dg = it & 7, qi = q0 + row;
-    if (qi < N) sum_store8<E>(smem, nw, SREG, row, dg, 1.f, o + ((long)b * N + qi) * os + head * HD + 8 * dg);
-  }
+  sum_store_queries(smem, nw, 64, o, b, head, N, q0, os);
 }
 
 // dQ: workgroup = 64 queries of one (b, head); wave w = key tile w; partial dQ summed in LDS
@@ -748,38 +812,13 @@ __global__ __launch_bounds__(64 * SKT) void sra_dq_small(const E* __restrict__ q
   char* Ki = smem + wave * SREG;
   char* Vi = Ki + KTILE * ROWB;
   const int t0 = wave * KTILE, nkw = min(KTILE, Nk - t0);
-  stage_rows<E>(k + ((long)b * Nk + t0) * kvs + head * HD, kvs, nkw, KTILE, Ki, 0, lane, 1);
-  stage_rows<E>(v + ((long)b * Nk + t0) * kvs + head * HD, kvs, nkw, KTILE, Vi, 0, lane, 1);
+  stage_kv(k, v, b, head, Nk, kvs, t0, nkw, KTILE, Ki, Vi, 0, lane, 1);
   frag8<E> qf[2][4], df[2][4];
   float Dq[2], lse2[2];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int qi = q0 + 32 * u + r;
-    const bool live = qi < N;
-    const E* qrow = q + ((long)b * N + qi) * qs + head * HD;
-    const E* orow = o + ((long)b * N + qi) * os + head * HD;
-    const E* drow = dout + ((long)b * N + qi) * dos + head * HD;
-    float dot = 0.f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (live) {
-        qf[u][s] = frag_bits<E>(*reinterpret_cast<const uint4*>(qrow + 16 * s + 8 * h));
-        df[u][s] = frag_bits<E>(*reinterpret_cast<const uint4*>(drow + 16 * s + 8 * h));
-        float x[8], y[8];
-        load_vec<E>(drow + 16 * s + 8 * h, x);
-        load_vec<E>(orow + 16 * s + 8 * h, y);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dot += x[j] * y[j];
-      } else {
-        qf[u][s] = df[u][s] = zfrag<E>();
-      }
-    }
-    dot += xor_lane<32>(dot);
-    Dq[u] = dot;
-    const long sidx = ((long)b * heads + head) * N + qi;
-    lse2[u] = live ? lse[sidx] * 1.4426950408889634f : 0.f;
-    if (live && h == 0 && wave == 0) Dws[sidx] = dot;
-  }
+  for (int u = 0; u < 2; ++u)
+    sra_dq_row(q, o, dout, lse, Dws, b, head, heads, N, q0 + 32 * u + r, qs, os, dos, h, h == 0 && wave == 0,
+               qf[u], df[u], Dq[u], lse2[u]);
   vm_wait<0>();
   f32x16 acc[2][2];
 #pragma unroll
@@ -801,19 +840,7 @@ __global__ __launch_bounds__(64 * SKT) void sra_dq_small(const E* __restrict__ q
         sa = MF<E>::mma(kf[s], qf[u][s], sa);
         dp = MF<E>::mma(vf[s], df[u][s], dp);
       }
-      const f2 sl2v = {sl2, sl2}, nl = {-lse2[u], -lse2[u]}, nD = {-Dq[u], -Dq[u]};
-#pragma unroll
-      for (int i = 0; i < 16; i += 2) {
-        const f2 a = f2{sa[i], sa[i + 1]} * sl2v + nl;
-        f2 p = {fexp2(a.x), fexp2(a.y)};
-        if (nkw < KTILE) {                       // the last wave's ragged tile (uniform branch)
-          if (32 * ks + accrow(i, h) >= nkw) p.x = 0.f;
-          if (32 * ks + accrow(i + 1, h) >= nkw) p.y = 0.f;
-        }
-        const f2 d = p * (f2{dp[i], dp[i + 1]} + nD);
-        ds[u][i] = d.x;
-        ds[u][i + 1] = d.y;
-      }
+      dq_ds_tile(sa, dp, ds[u], sl2, lse2[u], Dq[u], 32 * ks, nkw, h, nkw < KTILE);
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -833,11 +860,7 @@ __global__ __launch_bounds__(64 * SKT) void sra_dq_small(const E* __restrict__ q
     put_tile(Ki, acc[u][0], 32 * u, 0, lane, scale);
     put_tile(Ki, acc[u][1], 32 * u, 1, lane, scale);
   }
-  __syncthreads();
-  for (int it = threadIdx.x; it < 64 * 8; it += blockDim.x) {
-    const int row = it >> 3, dg = it & 7, qi = q0 + row;
-    if (qi < N) sum_store8<E>(smem, nw, SREG, row, dg, 1.f, dq + ((long)b * N + qi) * dqs + head * HD + 8 * dg);
-  }
+  sum_store_queries(smem, nw, 64, dq, b, head, N, q0, dqs);
 }
 
 // The same dQ with the two 32-query halves of a wave taken one after the other (their Q / dO
@@ -862,39 +885,16 @@ __global__ __launch_bounds__(64 * SKT, 2) void sra_dq_small_seq(const E* __restr
   char* Ki = smem + wave * SREG;
   char* Vi = Ki + KTILE * ROWB;
   const int t0 = wave * KTILE, nkw = min(KTILE, Nk - t0);
-  stage_rows<E>(k + ((long)b * Nk + t0) * kvs + head * HD, kvs, nkw, KTILE, Ki, 0, lane, 1);
-  stage_rows<E>(v + ((long)b * Nk + t0) * kvs + head * HD, kvs, nkw, KTILE, Vi, 0, lane, 1);
+  stage_kv(k, v, b, head, Nk, kvs, t0, nkw, KTILE, Ki, Vi, 0, lane, 1);
   f32x16 acc[NU][2];
 #pragma unroll
   for (int u = 0; u < NU; ++u) acc[u][0] = acc[u][1] = zero16();
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
-    const int qi = q0 + 32 * u + r;
-    const bool live = qi < N;
-    const E* qrow = q + ((long)b * N + qi) * qs + head * HD;
-    const E* orow = o + ((long)b * N + qi) * os + head * HD;
-    const E* drow = dout + ((long)b * N + qi) * dos + head * HD;
     frag8<E> qf[4], df[4];
-    float dot = 0.f;
-#pragma unroll
-    for (int s_ = 0; s_ < 4; ++s_) {
-      if (live) {
-        qf[s_] = frag_bits<E>(*reinterpret_cast<const uint4*>(qrow + 16 * s_ + 8 * h));
-        df[s_] = frag_bits<E>(*reinterpret_cast<const uint4*>(drow + 16 * s_ + 8 * h));
-        float x[8], y[8];
-        load_vec<E>(drow + 16 * s_ + 8 * h, x);
-        load_vec<E>(orow + 16 * s_ + 8 * h, y);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dot += x[j] * y[j];
-      } else {
-        qf[s_] = df[s_] = zfrag<E>();
-      }
-    }
-    dot += xor_lane<32>(dot);
-    const float Dq = dot;
-    const long sidx = ((long)b * heads + head) * N + qi;
-    const float lse2 = live ? lse[sidx] * 1.4426950408889634f : 0.f;
-    if (live && h == 0 && wave == 0) Dws[sidx] = dot;
+    float Dq, lse2;
+    sra_dq_row(q, o, dout, lse, Dws, b, head, heads, N, q0 + 32 * u + r, qs, os, dos, h, h == 0 && wave == 0,
+               qf, df, Dq, lse2);
     if (u == 0) vm_wait<0>();                  // (the K / V images of this wave have landed)
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -903,19 +903,7 @@ __global__ __launch_bounds__(64 * SKT, 2) void sra_dq_small_seq(const E* __restr
       for (int s_ = 0; s_ < 4; ++s_) sa = MF<E>::mma(frag_k<E>(Ki, 32 * ks, s_, lane), qf[s_], sa);
 #pragma unroll
       for (int s_ = 0; s_ < 4; ++s_) dp = MF<E>::mma(frag_k<E>(Vi, 32 * ks, s_, lane), df[s_], dp);
-      const f2 sl2v = {sl2, sl2}, nl = {-lse2, -lse2}, nD = {-Dq, -Dq};
-#pragma unroll
-      for (int i = 0; i < 16; i += 2) {
-        const f2 a = f2{sa[i], sa[i + 1]} * sl2v + nl;
-        f2 p = {fexp2(a.x), fexp2(a.y)};
-        if (nkw < KTILE) {                       // the last wave's ragged tile (uniform branch)
-          if (32 * ks + accrow(i, h) >= nkw) p.x = 0.f;
-          if (32 * ks + accrow(i + 1, h) >= nkw) p.y = 0.f;
-        }
-        const f2 d = p * (f2{dp[i], dp[i + 1]} + nD);
-        sa[i] = d.x;
-        sa[i + 1] = d.y;
-      }
+      dq_ds_tile(sa, dp, sa, sl2, lse2, Dq, 32 * ks, nkw, h, nkw < KTILE);   // dS over S, pair by pair
 #pragma unroll
       for (int s_ = 0; s_ < 2; ++s_) {
         const frag8<E> sf = MF<E>::from_acc(sa, s_);
@@ -930,11 +918,7 @@ __global__ __launch_bounds__(64 * SKT, 2) void sra_dq_small_seq(const E* __restr
     put_tile(Ki, acc[u][0], 32 * u, 0, lane, scale);
     put_tile(Ki, acc[u][1], 32 * u, 1, lane, scale);
   }
-  __syncthreads();
-  for (int it = threadIdx.x; it < 32 * NU * 8; it += blockDim.x) {
-    const int row = it >> 3, dg = it & 7, qi = q0 + row;
-    if (qi < N) sum_store8<E>(smem, nw, SREG, row, dg, 1.f, dq + ((long)b * N + qi) * dqs + head * HD + 8 * dg);
-  }
+  sum_store_queries(smem, nw, 32 * NU, dq, b, head, N, q0, dqs);
 }
 
 // dK / dV: workgroup = 32 keys of one (b, head) on the lanes; wave w sweeps query tiles
@@ -1079,6 +1063,28 @@ sraplan::SraKnobs sra_knobs() {
   return k;
 }
 
+// ---------------------------------------------------------------- launch dispatch
+template <typename E> struct Elem { using type = E; };
+template <int V> using Int = std::integral_constant<int, V>;
+
+// f(Elem<bf16 or f16>): the plan said SRA_FAST or SRA_SMALL, so dtype is 1 (bf16) or 2 (fp16)
+template <typename F>
+void by_dtype(int dtype, F&& f) {
+  if (dtype == 2) f(Elem<f16>{});
+  else f(Elem<bf16>{});
+}
+
+// f(Int<QW>, Int<NW>) for the plan's (qw, nw): the six instantiations of sra_fwd_fast / sra_dq_fast
+template <typename F>
+void by_qw_nw(int qw, int nw, F&& f) {
+  if (qw == 2 && nw == 4) f(Int<2>{}, Int<4>{});
+  else if (qw == 2) f(Int<2>{}, Int<8>{});
+  else if (nw == 10) f(Int<1>{}, Int<10>{});
+  else if (nw == 8) f(Int<1>{}, Int<8>{});
+  else if (nw == 4) f(Int<1>{}, Int<4>{});
+  else f(Int<1>{}, Int<2>{});                    // pick_nw returns 2, 4, 8 or 10
+}
+
 }  // namespace
 
 // the one launch decision of the SRA family (rules: sra_plan.h) under the live knobs and CU count;
@@ -1092,136 +1098,70 @@ int sra_dkv_fast_chunks(int Bt, int N, int Nk, int heads) {
   return sraplan::fast_dkv_chunks(Bt, N, Nk, heads, sra_knobs());
 }
 
-template <typename E>
-void sra_fwd_fast_launch_t(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
-                           int heads, long qs, long kvs, long os, float sl2, int qw, int nw, hipStream_t s) {
-  const int nkp = (Nk + KTILE - 1) / KTILE * KTILE;
-  const dim3 grid(cdiv(N, 32 * nw * qw), heads, Bt);
-#define CMX_SRA_FWD(QW_, NW_)                                                                                       \
-  hipLaunchKernelGGL((sra_fwd_fast<E, QW_, NW_>), grid, dim3(64 * NW_), 0, s, (const E*)q, (const E*)k,         \
-                     (const E*)v, (E*)o, lse, N, Nk, nkp, heads, qs, kvs, os, sl2)
-  if (qw == 2 && nw == 4) CMX_SRA_FWD(2, 4);
-  else if (qw == 2) CMX_SRA_FWD(2, 8);
-  else if (nw == 10) CMX_SRA_FWD(1, 10);
-  else if (nw == 8) CMX_SRA_FWD(1, 8);
-  else if (nw == 4) CMX_SRA_FWD(1, 4);
-  else CMX_SRA_FWD(1, 2);                        // pick_nw returns 2, 4, 8 or 10
-#undef CMX_SRA_FWD
+// The forward of an eligible problem (sra_plan.h: 16-bit storage, D = 64, 16-B aligned rows).
+// Short sequences (Nk <= 320, one 64-key tile per wave, N <= CMX_SRA_SMALL_N, default 2048: stages
+// 3 / 4 of B2 / B4) have their own kernels, but the forward takes its short-sequence kernel only up to
+// CMX_SRA_SMALL_FWD_N queries (default 600: stage 4; stage 3's N = 1200 runs the general LDS-resident
+// forward).  Measured standalone (profiles/r05_e_sra_standalone.txt, Bt = 4, Nk = 300): N = 1200 x 5
+// heads 16.0 us small vs 11.9 us fast; N = 300 x 8 heads 9.0 vs 10.6 us.  Both forwards sit at the same
+// error against fp64 at the B2 / B4 stage-3 / 4 shapes
+// (tests/test_gpu_kernels.py::test_sra_fwd_kernel_choice); the round-5 config-4 trip
+// (FRMs.3.channel_weights.mlp.0.bias ratio 18.4) was the parity test's ReLU-band cap, which now excludes
+// exactly the rows whose ReLU decision flipped
+void sra_lds_fwd(const SraArgs& a, const sraplan::SraPlan& plan) {
+  by_dtype(a.dtype, [&](auto elem) {
+    using E = typename decltype(elem)::type;
+    const E *q = (const E*)a.q, *k = (const E*)a.k, *v = (const E*)a.v;
+    if (plan.fwd == sraplan::SRA_SMALL) {
+      hipLaunchKernelGGL(sra_fwd_small<E>, dim3(cdiv(a.N, 64), a.heads, a.Bt), dim3(64 * cdiv(a.Nk, KTILE)), 0,
+                         a.stream, q, k, v, (E*)a.o, a.lse, a.N, a.Nk, a.heads, a.qs, a.kvs, a.os, a.sl2);
+      return;
+    }
+    const int nkp = (a.Nk + KTILE - 1) / KTILE * KTILE;
+    by_qw_nw(plan.qw, plan.nw, [&](auto qw, auto nw) {
+      constexpr int QW = decltype(qw)::value, NW = decltype(nw)::value;
+      hipLaunchKernelGGL((sra_fwd_fast<E, QW, NW>), dim3(cdiv(a.N, 32 * NW * QW), a.heads, a.Bt), dim3(64 * NW), 0,
+                         a.stream, q, k, v, (E*)a.o, a.lse, a.N, a.Nk, nkp, a.heads, a.qs, a.kvs, a.os, a.sl2);
+    });
+  });
 }
 
-template <typename E>
-void sra_dq_fast_launch_t(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                          const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                          long os, long dos, long dqs, float sl2, float scale, int qw, int nw, hipStream_t s) {
-  const int nkp = (Nk + KTILE - 1) / KTILE * KTILE;
-  const dim3 grid(cdiv(N, 32 * nw * qw), heads, Bt);
-#define CMX_SRA_DQ(QW_, NW_)                                                                                        \
-  hipLaunchKernelGGL((sra_dq_fast<E, QW_, NW_>), grid, dim3(64 * NW_), 0, s, (const E*)q, (const E*)k,          \
-                     (const E*)v, (const E*)o, (const E*)dout, lse, Dws, (E*)dq, N, Nk, nkp, heads, qs,  \
-                     kvs, os, dos, dqs, sl2, scale)
-  if (qw == 2 && nw == 4) CMX_SRA_DQ(2, 4);
-  else if (qw == 2) CMX_SRA_DQ(2, 8);
-  else if (nw == 10) CMX_SRA_DQ(1, 10);
-  else if (nw == 8) CMX_SRA_DQ(1, 8);
-  else if (nw == 4) CMX_SRA_DQ(1, 4);
-  else CMX_SRA_DQ(1, 2);                         // pick_nw returns 2, 4, 8 or 10
-#undef CMX_SRA_DQ
-}
-
-// partial dK / dV slabs of the query chunks (layout of sra_attention.hip's generic path); nchunk == 1:
-// the gradients themselves
-template <typename E>
-void sra_dkv_fast_launch_t(const void* q, const void* k, const void* v, const void* dout, const float* lse,
-                           const float* Dws, float* ws_dk, float* ws_dv, void* dk, void* dv, long dkvs, int Bt, int N,
-                           int Nk, int heads, long qs, long kvs, long dos, int nchunk, float sl2, float scale,
-                           hipStream_t s) {
-  const int nkw = ((Nk < NKP_MAX ? Nk : NKP_MAX) + 31) / 32 * 32;   // one 32-key sub-tile per wave
-  const int nkc = (Nk + NKP_MAX - 1) / NKP_MAX;                       // key chunks (Nk > NKP_MAX)
-  int qc = (N + nchunk - 1) / nchunk;
-  qc = (qc + QT - 1) / QT * QT;
-  hipLaunchKernelGGL(sra_dkv_fast<E>, dim3(nchunk * nkc, heads, Bt), dim3(2 * nkw), 0, s, (const E*)q, (const E*)k,
-                     (const E*)v, (const E*)dout, lse, Dws, ws_dk, ws_dv, (E*)dk, (E*)dv, dkvs, Bt, N,
-                     Nk, heads, qs, kvs, dos, qc, nchunk, sl2, scale);
-}
-
-// dtype 1 = bf16, 2 = fp16 (the plan said SRA_FAST); qw, nw: the plan's
-void sra_fwd_fast_launch(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
-                         int heads, long qs, long kvs, long os, float sl2, int qw, int nw, int dtype, hipStream_t s) {
-  if (dtype == 2) sra_fwd_fast_launch_t<f16>(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, qw, nw, s);
-  else sra_fwd_fast_launch_t<bf16>(q, k, v, o, lse, Bt, N, Nk, heads, qs, kvs, os, sl2, qw, nw, s);
-}
-
-void sra_dq_fast_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                        const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                        long os, long dos, long dqs, float sl2, float scale, int qw, int nw, int dtype,
-                        hipStream_t s) {
-  if (dtype == 2)
-    sra_dq_fast_launch_t<f16>(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, qw,
-                              nw, s);
-  else
-    sra_dq_fast_launch_t<bf16>(q, k, v, o, dout, lse, Dws, dq, Bt, N, Nk, heads, qs, kvs, os, dos, dqs, sl2, scale, qw,
-                               nw, s);
-}
-
-void sra_dkv_fast_launch(const void* q, const void* k, const void* v, const void* dout, const float* lse,
-                         const float* Dws, float* ws_dk, float* ws_dv, void* dk, void* dv, long dkvs, int Bt, int N,
-                         int Nk, int heads, long qs, long kvs, long dos, int nchunk, float sl2, float scale,
-                         int dtype, hipStream_t s) {
-  if (dtype == 2)
-    sra_dkv_fast_launch_t<f16>(q, k, v, dout, lse, Dws, ws_dk, ws_dv, dk, dv, dkvs, Bt, N, Nk, heads, qs, kvs, dos,
-                               nchunk, sl2, scale, s);
-  else
-    sra_dkv_fast_launch_t<bf16>(q, k, v, dout, lse, Dws, ws_dk, ws_dv, dk, dv, dkvs, Bt, N, Nk, heads, qs, kvs, dos,
-                                nchunk, sl2, scale, s);
-}
-
-// ---------------------------------------------------------------- short sequences (sra_*_small)
-// eligible (sra_plan.h): 16-bit storage, D = 64, Nk <= 320 (one 64-key tile per wave), 16-B aligned
-// rows, and a short query sequence (N <= CMX_SRA_SMALL_N, default 2048: stages 3 / 4 of B2 / B4).
-// The forward takes the short-sequence kernel only up to CMX_SRA_SMALL_FWD_N queries (default 600:
-// stage 4; stage 3's N = 1200 runs the general LDS-resident forward).  Measured standalone
-// (profiles/r05_e_sra_standalone.txt, Bt = 4, Nk = 300): N = 1200 x 5 heads 16.0 us small vs 11.9 us
-// fast; N = 300 x 8 heads 9.0 vs 10.6 us.  Both forwards sit at the same error against fp64 at the
-// B2 / B4 stage-3 / 4 shapes (tests/test_gpu_kernels.py::test_sra_fwd_kernel_choice); the round-5
-// config-4 trip (FRMs.3.channel_weights.mlp.0.bias ratio 18.4) was the parity test's ReLU-band cap,
-// which now excludes exactly the rows whose ReLU decision flipped
-void sra_fwd_small_launch(const void* q, const void* k, const void* v, void* o, float* lse, int Bt, int N, int Nk,
-                          int heads, long qs, long kvs, long os, float sl2, int dtype, hipStream_t s) {
-  const dim3 grid(cdiv(N, 64), heads, Bt), block(64 * cdiv(Nk, KTILE));
-  if (dtype == 2)
-    hipLaunchKernelGGL(sra_fwd_small<f16>, grid, block, 0, s, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)o,
-                       lse, N, Nk, heads, qs, kvs, os, sl2);
-  else
-    hipLaunchKernelGGL(sra_fwd_small<bf16>, grid, block, 0, s, (const bf16*)q, (const bf16*)k, (const bf16*)v,
-                       (bf16*)o, lse, N, Nk, heads, qs, kvs, os, sl2);
-}
-
-void sra_dq_small_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                         const float* lse, float* Dws, void* dq, int Bt, int N, int Nk, int heads, long qs, long kvs,
-                         long os, long dos, long dqs, float sl2, float scale, int seq, int dtype, hipStream_t s) {
-  const dim3 grid(cdiv(N, 64), heads, Bt), block(64 * cdiv(Nk, KTILE));
-  // seq (CMX_SRA_DQ_SEQ, default 1): sra_dq_small_seq (0: sra_dq_small)
-#define CMX_SRA_DQS(E_)                                                                                            \
-  if (seq) hipLaunchKernelGGL((sra_dq_small_seq<E_, 2>), grid, block, 0, s, (const E_*)q, (const E_*)k,            \
-                              (const E_*)v, (const E_*)o, (const E_*)dout, lse, Dws, (E_*)dq, N, Nk, heads, qs, kvs, \
-                              os, dos, dqs, sl2, scale);                                                            \
-  else hipLaunchKernelGGL(sra_dq_small<E_>, grid, block, 0, s, (const E_*)q, (const E_*)k, (const E_*)v,           \
-                          (const E_*)o, (const E_*)dout, lse, Dws, (E_*)dq, N, Nk, heads, qs, kvs, os, dos, dqs,     \
-                          sl2, scale)
-  if (dtype == 2) CMX_SRA_DQS(f16);
-  else CMX_SRA_DQS(bf16);
-#undef CMX_SRA_DQS
-}
-
-void sra_dkv_small_launch(const void* q, const void* k, const void* v, const void* dout, const float* lse,
-                          const float* Dws, void* dk, void* dv, long dkvs, int Bt, int N, int Nk, int heads, long qs,
-                          long kvs, long dos, float sl2, float scale, int dtype, hipStream_t s) {
-  const int nqt = cdiv(N, KTILE);
-  const dim3 grid(cdiv(Nk, 32), heads, Bt), block(64 * (nqt < SQW ? nqt : SQW));
-#define CMX_SRA_DKVS(E_)                                                                                           \
-  hipLaunchKernelGGL(sra_dkv_small<E_>, grid, block, 0, s, (const E_*)q, (const E_*)k, (const E_*)v,                \
-                     (const E_*)dout, lse, Dws, (E_*)dk, (E_*)dv, dkvs, N, Nk, heads, qs, kvs, dos, sl2, scale)
-  if (dtype == 2) CMX_SRA_DKVS(f16);
-  else CMX_SRA_DKVS(bf16);
-#undef CMX_SRA_DKVS
+// The backward of an eligible problem: dQ (which also writes Dq to a.Dws), then dK / dV.  Fast: the
+// dK / dV kernel writes plan.dkv_chunks partial slabs (layout of sra_attention.hip's general path, folded
+// by the caller), or with one chunk the gradients themselves
+void sra_lds_bwd(const SraArgs& a, const sraplan::SraPlan& plan) {
+  by_dtype(a.dtype, [&](auto elem) {
+    using E = typename decltype(elem)::type;
+    const E *q = (const E*)a.q, *k = (const E*)a.k, *v = (const E*)a.v, *o = (const E*)a.o, *dout = (const E*)a.dout;
+    if (plan.bwd == sraplan::SRA_SMALL) {
+      const dim3 grid(cdiv(a.N, 64), a.heads, a.Bt), block(64 * cdiv(a.Nk, KTILE));
+      // plan.dq_seq (CMX_SRA_DQ_SEQ, default 1): sra_dq_small_seq (0: sra_dq_small)
+      if (plan.dq_seq)
+        hipLaunchKernelGGL((sra_dq_small_seq<E, 2>), grid, block, 0, a.stream, q, k, v, o, dout, a.lse, a.Dws,
+                           (E*)a.dq, a.N, a.Nk, a.heads, a.qs, a.kvs, a.os, a.dos, a.dqs, a.sl2, a.scale);
+      else
+        hipLaunchKernelGGL(sra_dq_small<E>, grid, block, 0, a.stream, q, k, v, o, dout, a.lse, a.Dws, (E*)a.dq, a.N,
+                           a.Nk, a.heads, a.qs, a.kvs, a.os, a.dos, a.dqs, a.sl2, a.scale);
+      const int nqt = cdiv(a.N, KTILE);
+      hipLaunchKernelGGL(sra_dkv_small<E>, dim3(cdiv(a.Nk, 32), a.heads, a.Bt), dim3(64 * (nqt < SQW ? nqt : SQW)),
+                         0, a.stream, q, k, v, dout, a.lse, a.Dws, (E*)a.dk, (E*)a.dv, a.dkvs, a.N, a.Nk, a.heads,
+                         a.qs, a.kvs, a.dos, a.sl2, a.scale);
+      return;
+    }
+    const int nkp = (a.Nk + KTILE - 1) / KTILE * KTILE;
+    by_qw_nw(plan.qw, plan.nw, [&](auto qw, auto nw) {
+      constexpr int QW = decltype(qw)::value, NW = decltype(nw)::value;
+      hipLaunchKernelGGL((sra_dq_fast<E, QW, NW>), dim3(cdiv(a.N, 32 * NW * QW), a.heads, a.Bt), dim3(64 * NW), 0,
+                         a.stream, q, k, v, o, dout, a.lse, a.Dws, (E*)a.dq, a.N, a.Nk, nkp, a.heads, a.qs, a.kvs,
+                         a.os, a.dos, a.dqs, a.sl2, a.scale);
+    });
+    const int nchunk = plan.dkv_chunks;
+    const int nkw = ((a.Nk < NKP_MAX ? a.Nk : NKP_MAX) + 31) / 32 * 32;   // one 32-key sub-tile per wave
+    const int nkc = (a.Nk + NKP_MAX - 1) / NKP_MAX;                         // key chunks (Nk > NKP_MAX)
+    int qc = (a.N + nchunk - 1) / nchunk;
+    qc = (qc + QT - 1) / QT * QT;
+    hipLaunchKernelGGL(sra_dkv_fast<E>, dim3(nchunk * nkc, a.heads, a.Bt), dim3(2 * nkw), 0, a.stream, q, k, v, dout,
+                       a.lse, a.Dws, a.ws_dk, a.ws_dv, (E*)a.dk, (E*)a.dv, a.dkvs, a.Bt, a.N, a.Nk, a.heads, a.qs,
+                       a.kvs, a.dos, qc, nchunk, a.sl2, a.scale);
+  });
 }

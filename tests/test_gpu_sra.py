@@ -13,6 +13,7 @@ and restores what it found.  Then:
                    path (fp32): 1e-4 of max |expected|.
   uniform          |lse - ln Nk| <= 2e-5 (a phantom key moves it by >= 9.8e-4), o within one ulp,
                    the backward as for random.
+  both dQ forms    where a case runs sra_dq_small_seq and sra_dq_small, their dq is bit-equal.
   containment      every tensor inside a larger buffer (320 rows of padding either side, row strides
                    C + 8 / 2C + 8, NaN around the inputs, a sentinel around the outputs): nothing
                    outside the logical tensors changes, the inputs are unchanged, the results are
@@ -100,6 +101,8 @@ def run_case(K, case, kind, dtype, dev):
                 assert_plan(K, case, dtype, dq_seq=bool(seq))
                 outs.append(run_packed(K, case, exp.x, dtype, dev))
                 check(case, kind, dtype, exp, outs[-1], f"dq_seq={seq}")
+            # sra_dq_small_seq keeps sra_dq_small's MFMA order per output element: the same bits
+            assert torch.equal(bits(outs[0].dq), bits(outs[1].dq)), f"{case.name} {kind}: dq of dq_seq=1 and 0 differ"
             return outs[0]
         assert_plan(K, case, dtype)
         got = run_packed(K, case, exp.x, dtype, dev)
