@@ -2,6 +2,8 @@
 
 The argument/return types are derived by parsing ``include/cmx_hip.h`` (shipped inside
 the package as ``cmx_hip.h``), so the header is the single source of truth for the ABI.
+``include/cmx_ohem.h`` (part 2 of the same library's ABI: the OHEM loss and its select) is parsed the
+same way into a table of its own, ``OHEM_SIGNATURES``; its entry points are called like any other.
 
 ``call`` / ``try_call`` / ``query`` / ``refusable`` take an entry point's name and its arguments in
 header order; ``marshal`` converts them by the kind the header declares for each parameter:
@@ -30,6 +32,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _VARIANT = os.environ.get("CMX_LIB_VARIANT", "")
 LIB_PATH = os.path.join(_HERE, f"libcmx_hip_{_VARIANT}.so" if _VARIANT else "libcmx_hip.so")
 HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_hip.h"), os.path.join(_HERE, "cmx_hip.h")]
+OHEM_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_ohem.h"), os.path.join(_HERE, "cmx_ohem.h")]
 
 
 class CMXError(RuntimeError):
@@ -71,7 +74,8 @@ def _header(path: str | None) -> str:
 
 
 def parse_header(path: str | None = None):
-    """Return {name: Signature (restype, [argtypes]), .kinds} for every declaration in cmx_hip.h."""
+    """Return {name: Signature (restype, [argtypes]), .kinds} for every declaration in the header at
+    ``path`` (default: cmx_hip.h)."""
     text = re.sub(r"/\*.*?\*/", "", _header(path), flags=re.S)
     out = {}
     for m in re.finditer(r"^\s*([A-Za-z_][\w\s\*]*?)\b(cmx_\w+)\s*\(([^)]*)\)\s*;", text, re.M):
@@ -103,15 +107,17 @@ def _load():
         raise CMXError(f"{LIB_PATH} was built for C-ABI revision {have}, the header declares {want}: "
                        "rebuild it (`make -C rgbx_semantic_segmentation_amd/csrc`)")
     sigs = parse_header()
-    for name, (rt, argt) in sigs.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argt
-        fn.restype = rt
-        assert STREAM not in sigs[name].kinds[:-1], f"{name}: hipStream_t must be the last parameter"
-    return lib, sigs
+    ohem = parse_header(next(p for p in OHEM_HEADER_PATHS if os.path.exists(p)))
+    for table in (sigs, ohem):
+        for name, (rt, argt) in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argt
+            fn.restype = rt
+            assert STREAM not in table[name].kinds[:-1], f"{name}: hipStream_t must be the last parameter"
+    return lib, sigs, ohem
 
 
-LIB, SIGNATURES = _load()
+LIB, SIGNATURES, OHEM_SIGNATURES = _load()
 
 
 def last_error() -> str:
@@ -138,7 +144,7 @@ def _scalar_arg(a):
 
 # per entry point, built once: (the C function, one converter per parameter, takes a trailing stream)
 _BOUND = {name: (getattr(LIB, name), tuple(_pointer_arg if k == POINTER else _scalar_arg for k in sig.kinds),
-                 sig.kinds[-1:] == (STREAM,)) for name, sig in SIGNATURES.items()}
+                 sig.kinds[-1:] == (STREAM,)) for name, sig in {**SIGNATURES, **OHEM_SIGNATURES}.items()}
 
 
 def marshal(name: str, args: tuple) -> tuple:

@@ -32,6 +32,18 @@
 //   LK_DICE   the gradient pass, after dice_finalize_kernel made the coefficient table from the folded
 //             statistics: dst = the adjoint of dL_dice/dz + cen (p - onehot), cen = ce_scale / n_valid;
 //             the table (cw: per image c'[K], a'[K], cen; c', a' = dice_scale * c, a) is read from LDS
+//
+// ProbOhemCrossEntropy2d (utils/loss_opr.py:205-255; ohem_fused.hip) needs a global order statistic:
+// with valid = (y != ignore and 0 <= y < K) (NLLLoss's rule) and p_y the valid pixels' target-class
+// probability, kept = valid and p_y <= threshold, threshold = max(thresh, min_kept-th smallest p_y)
+// (+inf when min_kept <= 0 or min_kept > n_valid: nothing is dropped), loss = mean over kept of -log p_y,
+// dl/dz_j = (p_j - [j = y]) / n_kept at kept pixels, 0 elsewhere.  Two criteria of the template serve it:
+//   LK_OSTAT  the statistics pass: py (B, H, W) fp32 = p_y of every pixel the tile owns (2.0 at a pixel
+//             that is not valid) and the integer counts of the valid pixels and of those with
+//             p_y <= thresh; ends after pass 2, no adjoint (t1 is never touched)
+//   LK_OHEM   the gradient pass, after the select made the threshold: LK_CE's body with the pixels
+//             whose stored py exceeds the device scalar threshold treated as ignored; no probability is
+//             recomputed for the decision, so the two passes agree by construction
 #pragma once
 #include "cmx_common.h"
 
@@ -56,8 +68,10 @@ constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.69314718055994531f;
 constexpr float FEPS = 1e-8f;
 
 // LK_CE is internal: cmx_upsample_loss_fwd_adj's `kind` is 0..2
-enum { LK_CE = -1, LK_WCE = 0, LK_FL2D = 1, LK_FOCAL = 2, LK_DICE = 3, LK_DSTAT = 4 };
+enum { LK_CE = -1, LK_WCE = 0, LK_FL2D = 1, LK_FOCAL = 2, LK_DICE = 3, LK_DSTAT = 4, LK_OHEM = 5, LK_OSTAT = 6 };
 template <int LK> constexpr bool lk_dice = LK == LK_DICE || LK == LK_DSTAT;
+template <int LK> constexpr bool lk_ce = LK == LK_CE || LK == LK_OHEM;   // the plain-CE body
+constexpr float OHEM_SENTINEL = 2.f;    // py of a pixel that is not valid: above every probability
 // gamma paths of kind 2: integer powers for 0, 1, 2, 4; GP_GEN = exp2(gamma * log2 x), gamma > 1
 enum { GP_GEN = -1 };
 
@@ -141,6 +155,10 @@ __device__ __forceinline__ float target_nll(const float* la, const float* lb, in
 //                (softmax - onehot) * dloss[0] * stats[1]
 //   LK_DSTAT:    part[dice_part_stride(K) blk ..] = the block's statistics partials; dst unused
 //   LK_DICE:     cw = the coefficient table; dst as FWD = true, final up to dloss; part unused
+//   LK_OSTAT:    dst = py (B, H, W) fp32; part = two unsigned counters [n_valid, n_below], zeroed by the
+//                caller, one integer atomic per block and counter; gamma = thresh
+//   LK_OHEM:     cw = py, stats = the threshold (one float); dst and part as LK_CE with FWD = true, the
+//                normaliser being the kept count
 // cw, gamma, alpha, cs, fs: the criterion's parameters (see the top); LK_CE reads none of them.
 template <typename T, int LK, int GP, bool FWD>
 __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits, const int64_t* __restrict__ label,
@@ -171,12 +189,16 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
   // branch and waited for there, 4 + NL round trips one after another
   long lab[4];
   bool labok[4];
+  float pyv[4];                                   // LK_OHEM: the pixels' stored p_y
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int X = X0 + j;
     labok[j] = rowin && X >= 0 && X < W;
     lab[j] = label[labok[j] ? ((long)b * H + Y) * W + X : (long)b * H * W];
+    if constexpr (LK == LK_OHEM) pyv[j] = cw[labok[j] ? ((long)b * H + Y) * W + X : (long)b * H * W];
   }
+  float thr = 0.f;
+  if constexpr (LK == LK_OHEM) thr = stats[0];
   const T* base = logits + (long)b * h * w * K;
   constexpr int NL = (LP * KF + CT_NT - 1) / CT_NT;
   float v[NL];
@@ -216,6 +238,8 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
     cr[j] = (i0 == xr ? l0 : 0.f) + (i1 == xr ? l1 : 0.f);
     if constexpr (LK == LK_FOCAL || lk_dice<LK>)  // FocalLoss: clamp(label, 0, K - 1), invalid only at ignore
       lv[j] = (labok[j] && lab[j] != ignore) ? (int)(lab[j] < 0 ? 0L : (lab[j] > K - 1 ? (long)(K - 1) : lab[j])) : -1;
+    else if constexpr (LK == LK_OHEM)             // NLLLoss's rule and the select's: kept <=> py <= threshold
+      lv[j] = (labok[j] && lab[j] >= 0 && lab[j] < K && lab[j] != ignore && pyv[j] <= thr) ? (int)lab[j] : -1;
     else                                          // NLLLoss
       lv[j] = (labok[j] && lab[j] >= 0 && lab[j] < K && lab[j] != ignore) ? (int)lab[j] : -1;
   }
@@ -252,6 +276,12 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
     if (t < KF) tcnt_s[t] = 0;
     tcnt = tcnt_s;
     wsum = wsum_s;
+  }
+  unsigned* ocnt = nullptr;                       // LK_OSTAT: the block's [n_valid, n_below]
+  if constexpr (LK == LK_OSTAT) {
+    __shared__ unsigned ocnt_s[2];
+    if (t < 2) ocnt_s[t] = 0;
+    ocnt = ocnt_s;
   }
   __syncthreads();
   // pass 1: the run's two row-interpolated columns per class (registers, log2 units), the bound
@@ -294,6 +324,35 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
       for (int k = 0; k < KF; ++k)
         sv[j] += __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], ml[k], __builtin_fmaf(cr[j], mr[k], -m)));
     }
+  if constexpr (LK == LK_OSTAT) {
+    // p_y = e_y / sv of the pixels this tile owns, e_y formed exactly as class y's term of sv (so
+    // p_y <= 1: sv is a sum of non-negative terms that include e_y); every pixel of the image is owned
+    // by exactly one tile.  The counts are integers: order-independent
+    float* py = reinterpret_cast<float*>(dst);
+    const bool rown = Y >= 4 * y0 && Y < 4 * (y0 + CT_Y);
+    unsigned nv = 0, nb = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int X = X0 + j;
+      if (labok[j] && rown && X >= 4 * x0 && X < 4 * (x0 + CT_X)) {
+        float p = OHEM_SENTINEL;
+        if (lv[j] >= 0) {
+          const int q = lv[j] * LP;
+          const float mly = __builtin_fmaf(wa2, la[q], wb2 * lb[q]);
+          const float mry = __builtin_fmaf(wa2, la[q + 1], wb2 * lb[q + 1]);
+          p = __builtin_amdgcn_exp2f(__builtin_fmaf(cl[j], mly, __builtin_fmaf(cr[j], mry, -shv[j]))) / sv[j];
+          nv += 1;
+          nb += p <= gamma ? 1 : 0;
+        }
+        py[((long)b * H + Y) * W + X] = p;
+      }
+    }
+    if (nv) atomicAdd(&ocnt[0], nv);
+    if (nb) atomicAdd(&ocnt[1], nb);
+    __syncthreads();
+    if (t < 2 && ocnt[t]) atomicAdd(reinterpret_cast<unsigned*>(part) + t, ocnt[t]);
+    return;
+  }
   // gs: the scale of the whole gradient, a literal 1 in the forward.  The recompute backward folds
   // it into inv as gs / sv (not (1 / sv) * gs: the last bit differs)
   const float gs = FWD ? 1.f : dloss[0] * stats[1];
@@ -357,7 +416,7 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
   }
   // per pixel: pl = its loss, pn = its share of the normaliser, pc = the factor on (p - onehot)
   float pl[4], pn[4], pc[4], S[4];
-  if constexpr (LK == LK_CE) {
+  if constexpr (lk_ce<LK>) {
     // pl is formed below, for the pixels the tile owns only (no other use of the target logit)
 #pragma unroll
     for (int j = 0; j < 4; ++j) pc[j] = gs;
@@ -440,7 +499,7 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
     for (int j = 0; j < 4; ++j) {
       const int X = X0 + j;
       const bool own = lv[j] >= 0 && rown && X >= 4 * x0 && X < 4 * (x0 + CT_X);
-      if constexpr (LK == LK_CE) {
+      if constexpr (lk_ce<LK>) {
         if (own) {
           ls += target_nll(la, lb, lv[j] * LP, wa2, wb2, cl[j], cr[j], shv[j], sv[j]);
           lc += 1.f;
@@ -506,7 +565,7 @@ __global__ __launch_bounds__(CT_NT) void loss_cells(const T* __restrict__ logits
     float al[4], ar[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if constexpr (LK == LK_CE) {                // inv carries gs already
+      if constexpr (lk_ce<LK>) {                  // inv carries gs already
         al[j] = cl[j] * inv[j];
         ar[j] = cr[j] * inv[j];
       } else {

@@ -1705,6 +1705,46 @@ class UpsampleDiceF(Function):
         return _scale_adjoint(ctx, adj, dloss, out), None, None, None, None
 
 
+class UpsampleOhemF(Function):
+    """F.interpolate(logits, (H, W), bilinear) + ProbOhemCrossEntropy2d(thresh, min_kept)
+    (utils/loss_opr.py) fused (cmx_upsample_ohem_fwd_adj): a statistics pass writes every pixel's
+    target-class probability, a device radix select finds threshold = max(thresh, min_kept-th smallest),
+    and the gradient pass is plain CE over the pixels at or below it; the backward scales the fp32
+    bilinear adjoint by dloss / n_kept (cmx_upsample_ce_bwd_scale).  spec = (thresh, min_kept).  Nothing is
+    read back to the host: the regime is chosen on the device.  Without a backward to come the same
+    launches run and the adjoint is dropped.  No materialised fallback: outside H = 4h, W = 4w, K <= 40
+    this raises NotImplementedError.  ``last`` = (out, counts) of the latest forward: out =
+    [loss, 1 / n_kept, n_kept, threshold], counts = [n_valid, n_below, n_kept]."""
+
+    last = None
+
+    @staticmethod
+    def forward(ctx, logits, label, dims, ignore, spec):
+        B, h, w, H, W, Kc = dims
+        thresh, min_kept = spec
+        logits = _c(logits)
+        f32 = dict(dtype=torch.float32, device=logits.device)
+        out = torch.empty(4, **f32)
+        py = torch.empty(B, H, W, **f32)
+        counts = torch.empty(3, dtype=torch.int64, device=logits.device)
+        adj = torch.empty(B, h * w, Kc, **f32)
+        ws = K._ws(K.query("cmx_upsample_ohem_workspace", B, h, w), logits.device)
+        if K.refusable("cmx_upsample_ohem_fwd_adj", (K.CMX_ERR_SHAPE,), logits, label, adj, out, py, counts, ws, B, h, w,
+                       H, W, Kc, ignore, float(thresh), int(min_kept), K.dtype_code(logits)) is K.REFUSED:
+            raise NotImplementedError(f"fused upsample + OHEM loss: {K.last_error()}; only CrossEntropyLoss has "
+                                      "a materialised path for other shapes")
+        UpsampleOhemF.last = (out, counts)
+        ctx.save_for_backward(adj, out)
+        ctx.ldtype, ctx.lshape = logits.dtype, logits.shape
+        return out[0]             # a view of the kernel's result (no copy launch)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        adj, out = ctx.saved_tensors
+        dloss = _c(dloss.reshape(1).to(torch.float32))
+        return _scale_adjoint(ctx, adj, dloss, out), None, None, None, None
+
+
 def upsample_logits_nchw(logits, B, h, w, H, W, Kc):
     out = torch.empty(B, Kc, H, W, dtype=torch.float32, device=logits.device)
     K.call("cmx_bilinear_fwd_nchw_f32", _c(logits), out, B, h, w, H, W, Kc, K.dtype_code(logits))

@@ -74,7 +74,7 @@ DECODERS = {"MLPDecoder": MLPDecoder.DecoderHead, "MLPDecoderpp": MLPDecoderpp.D
 
 SUPPORTED_CRITERIA = ("nn.CrossEntropyLoss(reduction='mean'[, weight=w]), FocalLoss(reduction='mean', gamma == 0 or "
                       "gamma >= 1), FocalLoss2d(reduction='mean'[, weight=w]), DiceLoss(reduction='mean'), "
-                      "DiceCELoss(reduction='mean') and CE_Focal = the tuple "
+                      "DiceCELoss(reduction='mean'), ProbOhemCrossEntropy2d(reduction='mean') and CE_Focal = the tuple "
                       "(nn.CrossEntropyLoss(reduction='mean'), FocalLoss(...))")
 
 
@@ -84,12 +84,19 @@ class DiceSpec(tuple):
     __slots__ = ()
 
 
+class OhemSpec(tuple):
+    """UpsampleOhemF's (thresh, min_kept): a type of its own, as DiceSpec."""
+    __slots__ = ()
+
+
 def _loss_plan(criterion):
     """(ignore_index, spec, class weight) of a supported criterion (train.py:70-88), else
     NotImplementedError naming the supported set.  spec None: plain CrossEntropyLoss, the
-    UpsampleCEF path; a DiceSpec: DiceLoss / DiceCELoss, the UpsampleDiceF path; otherwise
-    UpsampleLossF's (kind, gamma, alpha, ce_scale, focal_scale)."""
-    from ..utils.loss_opr import CE_FOCAL_WEIGHT, DiceCELoss, DiceLoss, FocalLoss, FocalLoss2d, check_focal_gamma
+    UpsampleCEF path; a DiceSpec: DiceLoss / DiceCELoss, the UpsampleDiceF path; an OhemSpec:
+    ProbOhemCrossEntropy2d, the UpsampleOhemF path; otherwise UpsampleLossF's (kind, gamma, alpha,
+    ce_scale, focal_scale)."""
+    from ..utils.loss_opr import (CE_FOCAL_WEIGHT, DiceCELoss, DiceLoss, FocalLoss, FocalLoss2d,
+                                  ProbOhemCrossEntropy2d, check_focal_gamma)
 
     def refuse(why):
         raise NotImplementedError(f"criterion: {why}; on the hot path: {SUPPORTED_CRITERIA}")
@@ -137,6 +144,10 @@ def _loss_plan(criterion):
         if not 0.0 <= alpha <= 1.0:
             refuse(f"DiceCELoss(alpha={criterion.alpha!r})")
         return int(criterion.ce.ignore_index), DiceSpec((1.0 - alpha, alpha, smooth)), None
+    if isinstance(criterion, ProbOhemCrossEntropy2d):
+        if criterion.reduction != "mean":
+            refuse(f"ProbOhemCrossEntropy2d(reduction={criterion.reduction!r})")
+        return int(criterion.ignore_label), OhemSpec((float(criterion.thresh), int(criterion.min_kept))), None
     if isinstance(criterion, (tuple, list)) and len(criterion) == 2 and isinstance(criterion[1], FocalLoss) \
             and plain_ce(criterion[0]):
         ce, fl = criterion
@@ -345,4 +356,6 @@ class EncoderDecoder(nn.Module):
             return F.UpsampleCEF.apply(logits, label, dims, self.ignore_index)
         if isinstance(self._loss_spec, DiceSpec):
             return F.UpsampleDiceF.apply(logits, label, dims, self.ignore_index, self._loss_spec)
+        if isinstance(self._loss_spec, OhemSpec):
+            return F.UpsampleOhemF.apply(logits, label, dims, self.ignore_index, self._loss_spec)
         return F.UpsampleLossF.apply(logits, label, dims, self.ignore_index, self._loss_spec, self._loss_weight)

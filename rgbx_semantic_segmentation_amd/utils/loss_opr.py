@@ -5,7 +5,8 @@ signatures at the reference's import path.
 On the training hot path ``EncoderDecoder`` never calls these modules' ``forward``: it reads
 their hyper-parameters and runs ``cmx_upsample_loss_fwd_adj`` on the low-resolution logits
 (functions.UpsampleLossF; DiceLoss / DiceCELoss: ``cmx_upsample_dice_fwd_adj``,
-functions.UpsampleDiceF).  ``forward(pred, target)`` is the plain-PyTorch statement of the same
+functions.UpsampleDiceF; ProbOhemCrossEntropy2d: ``cmx_upsample_ohem_fwd_adj``,
+functions.UpsampleOhemF).  ``forward(pred, target)`` is the plain-PyTorch statement of the same
 math on full-resolution logits (B, K, H, W): API compatibility off the hot path, and the tests'
 fp64 reference.  ``focal_grad`` / ``focal2d_grad`` / ``dice_grad`` are the closed-form gradients
 the kernels implement.
@@ -122,6 +123,49 @@ class DiceCELoss(nn.Module):
 
     def forward(self, preds, targets):
         return self.alpha * self.dice(preds, targets) + (1 - self.alpha) * self.ce(preds, targets)
+
+
+class ProbOhemCrossEntropy2d(nn.Module):
+    """Online hard example mining on plain CrossEntropyLoss: the mean of -log p_y over the KEPT pixels.
+    valid = (target != ignore_label and 0 <= target < K) -- a label outside [0, K) counts as ignored, as
+    the fused plain-CE path does; p_y = the softmax probability of the pixel's own class.
+      min_kept > n_valid, min_kept <= 0 or n_valid == 0: nothing is filtered, the result is
+        CrossEntropyLoss(mean) (NaN when nothing is valid);
+      otherwise threshold = max(thresh, min_kept-th smallest p_y over the valid pixels) and
+        kept = valid and p_y <= threshold: ties at the threshold are all kept.
+    The mask is a constant for autograd.  ``down_ratio`` is stored and unused, as in the reference;
+    ``use_weight=True`` (the reference's 19-entry Cityscapes table) is not carried over."""
+
+    def __init__(self, ignore_label, reduction='mean', thresh=0.6, min_kept=256, down_ratio=1, use_weight=False):
+        super().__init__()
+        if use_weight:
+            raise NotImplementedError("ProbOhemCrossEntropy2d(use_weight=True): the class-weight table is not supported")
+        self.ignore_label = ignore_label
+        self.thresh = float(thresh)
+        self.min_kept = int(min_kept)
+        self.down_ratio = down_ratio
+        self.reduction = reduction
+        self.criterion = nn.CrossEntropyLoss(reduction=reduction, ignore_index=ignore_label)
+
+    @torch.no_grad()
+    def selection(self, pred, target):
+        """(kept mask (B, H, W), threshold, n_valid, n_below) of the rule above; threshold is +inf when
+        nothing is filtered, n_below = #(valid and p_y <= thresh)."""
+        K = pred.shape[1]
+        valid = (target != self.ignore_label) & (target >= 0) & (target < K)
+        py = torch.softmax(pred, dim=1).gather(1, target.clamp(0, K - 1).unsqueeze(1)).squeeze(1)
+        pv = py[valid]
+        n_valid = int(pv.numel())
+        n_below = int((pv <= self.thresh).sum())
+        if self.min_kept <= 0 or self.min_kept > n_valid:
+            return valid, float("inf"), n_valid, n_below
+        kth = pv.kthvalue(self.min_kept).values.item()
+        threshold = kth if kth > self.thresh else self.thresh
+        return valid & (py <= threshold), threshold, n_valid, n_below
+
+    def forward(self, pred, target):
+        kept = self.selection(pred, target)[0]
+        return self.criterion(pred, torch.where(kept, target, torch.full_like(target, self.ignore_label)))
 
 
 # ------------------------------------------------------------------ closed-form gradients

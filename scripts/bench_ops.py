@@ -141,6 +141,62 @@ def dice():
     return res
 
 
+def ohem():
+    """ProbOhemCrossEntropy2d on the fused path (cmx_upsample_ohem_fwd_adj) at the B2 shape
+    (2, 120, 160, 40) bf16 on the inputs of tests/ohem_cases.py, for big_thresh (the digit passes return
+    at once) and big_kth (the full select): the whole sequence by HIP events, each launch's own device
+    time from a kernel trace of the same calls (torch.profiler), beside three yardsticks in the same
+    process: plain CE's training form, the Dice triple, and eager PyTorch OHEM forward + backward on the
+    materialised upsample."""
+    import torch.nn.functional as Fn
+    from torch.profiler import ProfilerActivity, profile
+    sys.path.insert(0, "tests")
+    import ohem_cases as oc
+    B, h, w, Kc = oc.BIG
+    H, W = 4 * h, 4 * w
+    lg, lab = oc.make_inputs(oc.BIG)
+    logits, label = lg.to("cuda", torch.bfloat16).contiguous(), lab.cuda()
+    out, counts = torch.empty(4, device="cuda"), torch.empty(3, dtype=torch.int64, device="cuda")
+    py, adj = torch.empty(B, H, W, device="cuda"), torch.empty(B, h * w, Kc, device="cuda")
+    stats = torch.empty(B, Kc, 3, device="cuda")
+    ws = K._ws(max(K.query("cmx_upsample_ohem_workspace", B, h, w), K.query("cmx_upsample_dice_workspace", B, h, w, Kc),
+                   K.query("cmx_upsample_ce_workspace", B, H, W)), "cuda")
+    res = {}
+    for name in oc.BIG_CASES:
+        c = oc.CASES[name]
+        fused = lambda: K.call("cmx_upsample_ohem_fwd_adj", logits, label, adj, out, py, counts, ws, B, h, w, H, W, Kc,
+                               oc.IGNORE, c.thresh, c.min_kept, 1)
+        res[f"ohem {name} (all launches)"] = timeit(fused)
+        assert counts.tolist() == [c.n_valid, c.n_below, c.n_kept], counts.tolist()
+        n = 20
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(n):
+                fused()
+            torch.cuda.synchronize()
+        for ev in prof.key_averages():
+            t = getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+            if ev.count == n and t > 0:
+                # loss_cells<bf16, LK_OSTAT = 6 / LK_OHEM = 5, 0, true>, demangled or not
+                kind = ("statistics pass" if ("Li6ELi0" in ev.key or ", 6, 0," in ev.key)
+                        else "gradient pass" if ("Li5ELi0" in ev.key or ", 5, 0," in ev.key)
+                        else next((s for s in ("ohem_hist_kernel<0>", "ohem_hist_kernel<1>", "ohem_hist_kernel<2>",
+                                               "ohem_final", "loss_finalize", "ohem_zero") if s in ev.key), ev.key[:40]))
+                res[f"  {name} launch: {kind}"] = t / n
+        eager = oc.make_criterion(name).cuda()
+        x = logits.view(B, h, w, Kc).permute(0, 3, 1, 2).float().requires_grad_(True)
+
+        def step():
+            x.grad = None
+            up = Fn.interpolate(x, size=(H, W), mode="bilinear", align_corners=False)
+            eager(up, label).backward()
+        res[f"eager fwd+bwd OHEM {name}"] = timeit(step, iters=10)
+    res["ce_fwd_adj (plain CE)"] = timeit(lambda: K.call(
+        "cmx_upsample_ce_fwd_adj", logits, label, adj, out, ws, B, h, w, H, W, Kc, 255, 1))
+    res["dice training (3 launches)"] = timeit(lambda: K.call(
+        "cmx_upsample_dice_fwd_adj", logits, label, adj, out, stats, ws, B, h, w, H, W, Kc, 255, 0.5, 0.5, 1e-6, 1))
+    return res
+
+
 def decoder():
     """The decoder fold's full-resolution passes at the B2 shapes: the upsample-sum (up3) + the c1
     residual GEMM against the c1 GEMM with the upsample in its epilogue, and the 3-grid adjoint
