@@ -241,6 +241,17 @@ __device__ __forceinline__ float group_sum(float v, int width) {
 }
 __device__ __forceinline__ float wave_sum(float v) { return group_sum(v, 64); }
 
+// ---------------------------------------------------------------- counter-based random draws
+// uniform [0, 1) from splitmix64 of (seed, step, element): the generator of every stochastic mask
+// (cmx_step_masks, cmx_easpp_dropout_mask); the step lives on the device, so a graph replay draws afresh
+__device__ __forceinline__ float u01(unsigned long long seed, unsigned long long step, unsigned long long i) {
+  unsigned long long z = seed ^ (step * 0x9E3779B97F4A7C15ull) ^ (i * 0xD1B54A32D192ED03ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (float)(z >> 40) * (1.f / 16777216.f);   // 24 random bits -> [0, 1)
+}
+
 // Branch-free fp32 erf: x * P(x^2) / Q(x^2) on x clamped to [-4, 4] (the rational minimax
 // form used by Eigen's fast float erf); max |error| 4.2e-7 against libm erf on [-6, 6]
 // (checked in tests/test_oracle_kats.py::test_fast_erf_table).  ocml's erff branches on the

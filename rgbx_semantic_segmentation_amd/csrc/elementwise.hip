@@ -147,17 +147,9 @@ static int colsum_nblk(long M) {
 //   DropPath (timm drop_path, dual_segformer.py:141-180): dp[i] = floor(keep[i] + u) / keep[i]
 //   Dropout2d (MLPDecoder.py:63, per sample and channel): d2[i] = (u >= p) / (1 - p)
 // and bumps the BN num_batches_tracked counter (BatchNorm2d.forward in train mode).  u is a
-// counter-based uniform draw: splitmix64 of (seed, step, element), the step counter kept on
+// counter-based uniform draw (u01, cmx_common.h) of (seed, step, element), the step counter kept on
 // the device, so a HIP-graph replay draws fresh masks with no host involvement.  One block:
 // every thread reads the step before thread 0 advances it.
-__device__ __forceinline__ float u01(unsigned long long seed, unsigned long long step, unsigned long long i) {
-  unsigned long long z = seed ^ (step * 0x9E3779B97F4A7C15ull) ^ (i * 0xD1B54A32D192ED03ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (float)(z >> 40) * (1.f / 16777216.f);   // 24 random bits -> [0, 1)
-}
-
 __global__ __launch_bounds__(256) void step_masks_kernel(const float* __restrict__ keep, int nkeep,
                                                          float* __restrict__ dp, int nd2, float p,
                                                          float* __restrict__ d2, unsigned long long seed,

@@ -116,6 +116,25 @@ def step_work(backbone="mit_b2", H=480, W=640, B=2, K=40, E=512, n_params=None):
         gemm(M, C, C, 1)                                                              # channel_embed[3]
         bn(M, C)
         bn(M, C, res=True)
+        if s == 3 and backbone.endswith("_w_ef_aspp"):
+            # eASPP neck: entry / exit / projection 1x1 convs on the GEMM family; per depth level the grouped dilated
+            # conv (fwd x, W -> y; dgrad; wgrad with fp32 dW), counted with all nine taps; the pooled branch's pool,
+            # its fp32 tiny linear, the concat assembly and its split; the dropout scale (fp32, written and read twice)
+            for n_out in (256, 64, 64, 64):
+                gemm(M, n_out, C, 1, bias_grad=False)
+                bn(M, n_out)
+            for _ in range(3 * 3):          # (depth level, branch)
+                mac2, wsz = 2 * M * 9 * 64 * 64, 9 * 64 * 64
+                add("easpp", 3 * mac2, A * (2 * M * 64 + wsz) * 2 + A * 2 * M * 64 + F32 * wsz)
+                bn(M, 64)
+            for _ in range(3):
+                gemm(M, 256, 64, 1, bias_grad=False)
+                bn(M, 256)
+            add("easpp", 3 * 2 * B * 256 * C, A * M * C * 2 + F32 * 3 * 256 * C)      # pool + 1x1 conv, fwd + bwd
+            add("easpp", 0, A * M * (4 * 256 + 1280) * 2)                               # concat fwd, split bwd
+            gemm(M, C, 1280, 1, bias_grad=False)
+            bn(M, C)
+            add("easpp", 0, F32 * M * C * 3)
         cin = C
     # decoder: linear_c1..4 at their own resolution, the fuse (c1 product + low-res products +
     # bilinear adds in the epilogue; adjoints in the backward), BN (+ReLU, Dropout2d), linear_pred

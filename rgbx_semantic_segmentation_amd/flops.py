@@ -11,6 +11,14 @@ def _grid(H, W, k, s, p):
     return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
 
 
+def easpp_macs(N, C) -> int:
+    """The eASPP neck on an N-pixel, C-channel map (dual_segformer_w_ef_aspp.py:48-157): the four 1x1 convs that read
+    it (256 + 3 * 64 outputs), nine dilated 3x3 64 -> 64 convs, three 64 -> 256 exits, the 1280 -> C projection, and
+    the pooled branch's 1x1 conv on one pixel.  Taps that fall outside the map are counted, as the reference runs
+    them."""
+    return N * (C * 448 + 9 * 9 * 64 * 64 + 3 * 64 * 256 + 1280 * C) + C * 256
+
+
 def forward_macs_per_image(backbone="mit_b2", H=480, W=640, K=40, E=512) -> int:
     dims, depths = MIT_SPECS[backbone]["embed_dims"], MIT_SPECS[backbone]["depths"]
     total = 0
@@ -36,6 +44,8 @@ def forward_macs_per_image(backbone="mit_b2", H=480, W=640, K=40, E=512) -> int:
         d = C // NUM_HEADS[s]
         total += 2 * N * C * C + 2 * N * C + 24 * C * C        # FRM
         total += 17 * N * C * C + 4 * N * C * d + 9 * N * C    # FFM
+        if s == 3 and backbone.endswith("_w_ef_aspp"):
+            total += easpp_macs(N, C)
         cin = C
     N1 = grids[0][0]
     total += sum(N * C * E for N, C in grids) + N1 * 4 * E * E + N1 * E * K

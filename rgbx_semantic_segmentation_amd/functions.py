@@ -1331,6 +1331,109 @@ def se_gate(store, att, y, dscale=None):
     return SEGateF.apply(y, prm, dscale, c1.weight)
 
 
+# ---------------------------------------------------------------------------- eASPP neck
+class DilatedConv3F(Function):
+    """The ASPPConv 3x3 convolutions (dilation = padding = rate, dual_segformer_w_ef_aspp.py:18-28) of the three
+    branches at one depth level: forward, input gradient and weight gradient each as ONE grouped launch
+    (cmx_easpp_conv_*; the weight gradient folds its per-workgroup partials in a second one).  x_g (B*h*w, 64),
+    Ws / Wgs: the branches' tap-major weights and their fp32 gradient views."""
+
+    @staticmethod
+    def forward(ctx, geom, Ws, Wgs, a0, a1, a2, x0, x1, x2):
+        B, h, w, rates = geom
+        xs = (x0, x1, x2)
+        ys = tuple(torch.empty_like(x) for x in xs)
+        K.easpp_conv("cmx_easpp_conv_fwd", xs, Ws, ys, B, h, w, rates)
+        ctx.save_for_backward(*xs)
+        ctx.meta = (geom, Ws, Wgs)
+        return ys
+
+    @staticmethod
+    def backward(ctx, *dys):
+        xs = ctx.saved_tensors
+        (B, h, w, rates), Ws, Wgs = ctx.meta
+        dys = tuple(_c(d) for d in dys)
+        dxs = tuple(torch.empty_like(x) for x in xs)
+        K.easpp_conv("cmx_easpp_conv_dgrad", dys, Ws, dxs, B, h, w, rates)
+        K.easpp_conv_wgrad(dys, xs, Wgs, B, h, w, rates)
+        return (None,) * 6 + dxs
+
+
+def dilated_conv3(store, convs, xs, B, h, w):
+    """DilatedConv3F on the three branches' nn.Conv2d modules ``convs`` (3x3, 64 -> 64, one dilation each)."""
+    Ws = tuple(store.w(c.weight, stacked=False) for c in convs)
+    Wgs = tuple(store.g(c.weight, stacked=False) for c in convs)
+    geom = (B, h, w, tuple(int(c.dilation[0]) for c in convs))
+    return DilatedConv3F.apply(geom, Ws, Wgs, *(c.weight for c in convs), *xs)
+
+
+class PooledConvF(Function):
+    """AsppPooling's AdaptiveAvgPool2d(1) and bias-free 1x1 conv (:31-45) on x (B*N, C): z (B, Cout) fp32 =
+    mean_n(x) W^T on the fp32 master weight (cmx_se_pool_fwd, cmx_small_linear_fwd).  Backward: the tiny linear's
+    one-pass backward (dW into the gradient buffer, dx as slices), then the pooling's adjoint, which sums the slices
+    (cmx_easpp_pool_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, W, Wg, B, N, anchor):
+        x = _c(x)
+        C = x.shape[-1]
+        pooled = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        ws = K._ws(K.query("cmx_se_pool_workspace", B, N, C), x.device)
+        K.call("cmx_se_pool_fwd", x, pooled, ws, se_tickets(anchor, x, B, C), B, N, C, K.dtype_code(x))
+        z = K.small_linear_fwd(pooled, W, None, W.shape[0])
+        ctx.save_for_backward(pooled, z, W)
+        ctx.meta = (Wg, B, N, x.dtype)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        pooled, z, W = ctx.saved_tensors
+        Wg, B, N, dtype = ctx.meta
+        C, Cout = pooled.shape[1], W.shape[0]
+        dpp = K.small_linear_bwd(_c(dz), 1, 0, Cout, z, pooled, W, Wg, None, Cout)
+        dx = torch.empty(B * N, C, dtype=dtype, device=dz.device)
+        K.call("cmx_easpp_pool_bwd", dpp, dpp.shape[0], B * C, dx, B, N, C, K.dtype_code(dx))
+        return dx, None, None, None, None, None
+
+
+def pooled_conv(store, conv, x, B, N):
+    """PooledConvF with the 1x1 nn.Conv2d ``conv`` of AsppPooling.gap."""
+    return PooledConvF.apply(x, store.w(conv.weight, stacked=False, compute=False),
+                             store.g(conv.weight, stacked=False), B, N, conv.weight)
+
+
+class EasppConcatF(Function):
+    """cat[x_in, b1, b2, b3, pool] (:152) with the pooled branch's bilinear upsample of a 1x1 map, a broadcast
+    (:44), in one launch: y_i (B*N, Cm), pool (B, Cm) fp32 -> (B*N, 5 Cm).  Backward, one launch: the four column
+    slots and the pooled branch's sum over each image's pixels."""
+
+    @staticmethod
+    def forward(ctx, y0, y1, y2, y3, pool, B, N):
+        y0, y1, y2, y3, pool = (_c(t) for t in (y0, y1, y2, y3, pool))     # the entry point takes no strides
+        Cm = y0.shape[-1]
+        cat = torch.empty(B * N, 5 * Cm, dtype=y0.dtype, device=y0.device)
+        K.call("cmx_easpp_concat_fwd", y0, y1, y2, y3, pool, cat, B, N, Cm, K.dtype_code(y0))
+        ctx.meta = (B, N, Cm)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        B, N, Cm = ctx.meta
+        dcat = _c(dcat)
+        ds = tuple(torch.empty(B * N, Cm, dtype=dcat.dtype, device=dcat.device) for _ in range(4))
+        dpool = torch.empty(B, Cm, dtype=torch.float32, device=dcat.device)
+        K.call("cmx_easpp_concat_bwd", dcat, *ds, dpool, B, N, Cm, K.dtype_code(dcat))
+        return (*ds, dpool, None, None)
+
+
+def easpp_dropout_scale(state, n, p, device):
+    """The elementwise Dropout(p) of eASPP.project as batchnorm's dscale: n fp32 values (u >= p) / (1 - p) drawn on
+    the device (cmx_easpp_dropout_mask); state = (seed, (step, arrival counter) uint64 pair as int64)."""
+    scale = torch.empty(n, dtype=torch.float32, device=device)
+    K.call("cmx_easpp_dropout_mask", scale, n, float(p), state[0], state[1])
+    return scale
+
+
 # ---------------------------------------------------------------------------- decoder fuse
 def _adjoint_to(dZ, B, H1, W1, h, w, E):
     """up^T dZ: the bilinear adjoint of the (h, w) -> (H1, W1) upsample, (B, h*w, E) in dZ's

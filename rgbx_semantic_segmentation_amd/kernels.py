@@ -470,3 +470,18 @@ def decoder_fuse_fwd(e1, Wc1, bias, zs, H1, W1, hw):
     call("cmx_decoder_fuse_fwd", e1, Wc1, Z, bias, zs[0], zs[1], zs[2], B, H1, W1, *hw[2], *hw[1], *hw[0], E, Kd, Kd,
          Wc1.stride(0), dtype_code(e1))
     return Z
+
+
+# ------------------------------------------------------------------------------ eASPP neck (include/cmx_easpp.h)
+def easpp_conv(entry: str, a, Ws, out, B, h, w, rates):
+    """cmx_easpp_conv_fwd / cmx_easpp_conv_dgrad (``entry``) on the three branches' rows a[g] (B*h*w, 64 at any row
+    stride), tap-major weights Ws[g] (64, 3, 3, 64) and outputs out[g] (the caller's)."""
+    call(entry, *a, *Ws, *out, B, h, w, a[0].shape[-1], *rates, a[0].stride(0), out[0].stride(0), dtype_code(a[0]))
+    return out
+
+
+def easpp_conv_wgrad(dys, xs, Wgs, B, h, w, rates):
+    """Wgs[g] (fp32 (64, 3, 3, 64) views of the gradient buffer) = the branches' weight gradients (overwritten)."""
+    ws = _ws(query("cmx_easpp_conv_wgrad_workspace", B, h, w), xs[0].device)
+    call("cmx_easpp_conv_wgrad", *dys, *xs, *Wgs, ws, B, h, w, xs[0].shape[-1], *rates, dys[0].stride(0),
+         xs[0].stride(0), dtype_code(xs[0]))

@@ -18,6 +18,14 @@ Differences by design:
   * Decoder input channels come from the encoder's ``embed_dims`` (the reference's
     hard-coded [96,192,384,768] for mit_b4/b5, builder.py:66-75, cannot run; its mit_b1
     entry builds mit_b0, :84-87).
+  * ``mit_b{0..5}_w_ef_aspp`` (dual_segformer_w_ef_aspp.py): the same encoders with the eASPP neck on the stage-4
+    fused map; the same two differences hold (its hard-coded [96,192,384,768] and its b1 -> b0), FRM / FFM stay
+    selectable, and training with one image per batch raises ValueError (the pooled branch's BatchNorm, as in torch).
+    The pooled branch's 1x1 conv runs on cmx_small_linear, which takes at most 8 rows: with the neck a batch is at
+    most 8 images per GPU (more is refused with the library's shape error, not computed another way).  The random
+    mask of the neck's Dropout keeps a step counter on the device; it is made by the first training forward, which
+    must be an eager one (inside a graph capture it raises).
+    ``forced_masks["aspp_dropout"]``: an optional (B, h, w, C4) 0/1 mask of the neck's Dropout for tests.
   * compute dtype: ``cfg.compute_dtype`` ("float32" | "bfloat16" | "float16"); defaults to
     float16 when ``cfg.use_mixed_precision`` (the reference's fp16 autocast switch,
     config.py:61, train.py:185-198: fp16 storage, fp32 accumulation, with dynamic loss scaling
@@ -171,8 +179,8 @@ class EncoderDecoder(nn.Module):
         super().__init__()
         backbone = _get(cfg, "backbone", "mit_b2")
         if backbone not in BACKBONES:
-            raise NotImplementedError(f"backbone {backbone!r}: only the MiT family (mit_b0..b5) is on the "
-                                      "CMX hot path")
+            raise NotImplementedError(f"backbone {backbone!r}: only the MiT family (mit_b0..b5, and mit_b0..b5 + "
+                                      "'_w_ef_aspp') is on the CMX hot path")
         decoder = _get(cfg, "decoder", "MLPDecoder")
         if decoder not in DECODERS:
             raise NotImplementedError(f"decoder {decoder!r}: only {' and '.join(DECODERS)} are on the CMX hot path")
@@ -336,7 +344,10 @@ class EncoderDecoder(nn.Module):
         group = self.process_group if (self.sync_bn and self.training) else None
         if self.training and getattr(self, "_nbt", None) is not None and not self._nbt_bumped:
             self._nbt.add_(1)
-        feats, grids = self.backbone.run(self.store, images, B, H, W, self.training, dp)
+        # forced_masks["aspp_dropout"] (optional): the (B, h, w, C4) 0/1 mask of the eASPP neck's Dropout; without
+        # it the neck draws its mask on the device (eASPP.dropout_scale), inside a captured step too
+        am = self.forced_masks.get("aspp_dropout") if (self.training and self.forced_masks is not None) else None
+        feats, grids = self.backbone.run(self.store, images, B, H, W, self.training, dp, aspp_mask=am)
         logits = self.decode_head.run(self.store, feats, grids, B, self.training, dscale=d2, group=group)
         return logits, grids[0]
 

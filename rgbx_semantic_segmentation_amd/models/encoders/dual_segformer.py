@@ -95,8 +95,100 @@ class OverlapPatchEmbed(nn.Module):               # dual_segformer.py:183-225
         self.pad = patch_size // 2
 
 
+def _conv_bn_relu(cin, cout, k=1, rate=1):
+    """Bias-free conv (3x3: dilation = padding = rate), plain BatchNorm2d, ReLU: every unit of the eASPP neck."""
+    return nn.Sequential(nn.Conv2d(cin, cout, k, padding=rate if k > 1 else 0, dilation=rate if k > 1 else 1,
+                                   bias=False), nn.BatchNorm2d(cout), nn.ReLU(True))
+
+
+class ASPPConv(nn.Module):                        # dual_segformer_w_ef_aspp.py:18-28
+    def __init__(self, channels, rate):
+        super().__init__()
+        self.block = _conv_bn_relu(channels, channels, 3, rate)
+
+
+class AsppPooling(nn.Module):                     # dual_segformer_w_ef_aspp.py:31-45
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.gap = nn.Sequential(nn.AdaptiveAvgPool2d(1), *_conv_bn_relu(cin, cout))
+
+
+class eASPP(nn.Module):                           # dual_segformer_w_ef_aspp.py:48-157
+    """The "efficient ASPP" neck on the stage-4 fused map: a 1x1 entry, three branches 1x1 -> 3 dilated 3x3 -> 1x1 at
+    width 64 (one rate each), an image-pooling branch, and a 1x1 projection of their concat with an elementwise
+    Dropout(0.5).  Every norm is a plain nn.BatchNorm2d (never SyncBatchNorm, as in the reference); registration names
+    are the reference's, so its ``backbone.single_aspp.*`` keys load.
+
+    ``run`` in launches (training, M = B h w <= 600 rows, so every BatchNorm is one launch each way): the four 1x1
+    convs that read x as ONE multi GEMM, each depth level of the three branches as ONE grouped dilated convolution
+    (functions.DilatedConv3F), the three exit 1x1 convs as ONE multi GEMM, the pooled branch (pool, tiny linear, BN),
+    one launch that assembles the concat buffer with the pooled row broadcast, the projection GEMM, the dropout
+    mask, and the 18 BatchNorm + ReLU launches (the last one applies the dropout scale): 28 forward."""
+    reduce_dim, middle_dim = 64, 256
+
+    def __init__(self, channels, atrous_rates=(12, 24, 36)):
+        super().__init__()
+        r, m = self.reduce_dim, self.middle_dim
+        self.input_conv = _conv_bn_relu(channels, m)
+        for i, rate in enumerate(atrous_rates):
+            setattr(self, f"branch{i + 1}", nn.ModuleList(
+                [_conv_bn_relu(channels, r)] + [ASPPConv(r, rate) for _ in range(3)] + [_conv_bn_relu(r, m)]))
+        self.img_pooling = AsppPooling(channels, m)
+        self.project = nn.Sequential(*_conv_bn_relu(5 * m, channels), nn.Dropout(0.5))
+
+    def dropout_scale(self, n, device, mask=None):
+        """project's Dropout as F.batchnorm's elementwise dscale (n = rows * channels values): ``mask`` (0/1, any
+        shape of n elements) forced, else drawn on the device from a seed and a device-side step counter, so a replayed
+        HIP graph draws a fresh mask without a host copy.  The counter is made at the first call, which must be an
+        eager one: inside a graph capture it raises."""
+        p = self.project[3].p
+        if p <= 0:
+            return None
+        if mask is not None:
+            return (mask.to(device=device, dtype=torch.float32).reshape(-1) / (1 - p)).contiguous()
+        device = torch.device(device)
+        st = self.__dict__.get("_mask_state")
+        if st is None or st[1].device.type != device.type or device.index not in (None, st[1].device.index):
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                # made inside a capture the counter would live in the graph's pool, and its zero fill would be
+                # replayed: every replay would draw the first mask again
+                raise RuntimeError("eASPP: the dropout mask's device step counter must exist before a graph capture: "
+                                   "run one eager training step first")
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())       # from torch's host generator
+            st = self.__dict__["_mask_state"] = (seed, torch.zeros(2, dtype=torch.int64, device=device))
+        return F.easpp_dropout_scale(st, n, p, device)
+
+    def run(self, store, x, B, h, w, training, mask=None):
+        """x (B*h*w, C) tokens of the fused map -> the neck's output, same shape.  mask: a forced (B, h, w, C) 0/1
+        dropout mask (training only; None: drawn on the device)."""
+        M, N = B * h * w, h * w
+        if training and B == 1:
+            raise ValueError("eASPP: training needs more than 1 image per batch: the pooled branch's BatchNorm sees "
+                             "one value per channel (as torch.nn.BatchNorm2d refuses)")
+        br = (self.branch1, self.branch2, self.branch3)
+
+        def unit(seq, t, **kw):
+            return F.batchnorm(store, seq[1], t, training, act="relu", **kw)
+
+        xg = x.view(1, M, -1)
+        ys = F.glinear_multi(store, [(u[0].weight, None, xg) for u in (self.input_conv, *(b[0] for b in br))])
+        x_in = unit(self.input_conv, ys[0].view(M, -1))
+        t = [unit(b[0], y.view(M, -1)) for b, y in zip(br, ys[1:])]
+        for d in (1, 2, 3):
+            t = F.dilated_conv3(store, [b[d].block[0] for b in br], t, B, h, w)
+            t = [unit(b[d].block, y) for b, y in zip(br, t)]
+        ys = F.glinear_multi(store, [(b[4][0].weight, None, y.view(1, M, -1)) for b, y in zip(br, t)])
+        outs = [unit(b[4], y.view(M, -1)) for b, y in zip(br, ys)]
+        gap = self.img_pooling.gap
+        pool = F.batchnorm(store, gap[2], F.pooled_conv(store, gap[1], x, B, N), training, act="relu")
+        cat = F.EasppConcatF.apply(x_in, *outs, pool, B, N)
+        y = F.glinear(store, self.project[0].weight, None, cat.view(1, M, -1)).view(M, -1)
+        scale = self.dropout_scale(y.numel(), y.device, mask) if training else None
+        return unit(self.project, y, dscale=scale, rps=1)
+
+
 class RGBXTransformer(nn.Module):                 # dual_segformer.py:228-446
-    def __init__(self, embed_dims, depths, drop_path_rate=0.1, frm="FRM", ffm="FFM"):
+    def __init__(self, embed_dims, depths, drop_path_rate=0.1, frm="FRM", ffm="FFM", aspp=False):
         super().__init__()
         self.embed_dims, self.depths = list(embed_dims), list(depths)
         self.dp = drop_path_probs(depths, drop_path_rate)
@@ -116,6 +208,8 @@ class RGBXTransformer(nn.Module):                 # dual_segformer.py:228-446
         fuse = FeatureFusionModule if ffm == "FFM" else ImprovedFeatureFusionModule
         self.FRMs = nn.ModuleList([rect(d) for d in embed_dims])
         self.FFMs = nn.ModuleList([fuse(d, NUM_HEADS[s]) for s, d in enumerate(embed_dims)])
+        if aspp:    # the mit_b*_w_ef_aspp family (dual_segformer_w_ef_aspp.py:477): one neck, on the stage-4 fused map
+            self.single_aspp = eASPP(embed_dims[3], atrous_rates=(12, 24, 36))
         self.apply(init_segformer)
 
     # ------------------------------------------------------------------------ execution
@@ -168,11 +262,20 @@ class RGBXTransformer(nn.Module):                 # dual_segformer.py:228-446
                       ln_tail=tn)
         return x, (s_mlp, tap_m), tn
 
-    def run(self, store, images, B, H, W, training, dp_scales: Optional[torch.Tensor], bn_group=None):
+    def run(self, store, images, B, H, W, training, dp_scales: Optional[torch.Tensor], bn_group=None, aspp_mask=None):
         """images: (2*B, 3, H, W) fp32 NCHW (RGB batch then X batch), or the pair of (B, 3, H, W)
         batches (rgb, modal_x) read by the stage-1 im2col in place.
         dp_scales: (n_blocks_total, 2, 2*? ) per-block (attn, mlp) per-sample scales or None.
+        aspp_mask: a forced dropout mask of the eASPP neck (eASPP.run), for the backbones that have one.
         Returns the 4 fused maps [(B*N_s, C_s) tokens] and their grids."""
+        neck = getattr(self, "single_aspp", None)
+
+        def fuse(s, r, Hc, Wc):
+            o = self.FFMs[s].run(store, r, B, Hc, Wc, training)
+            if s == 3 and neck is not None:      # :583-585, on the stream that produced the fused map
+                o = neck.run(store, o, B, Hc, Wc, training, mask=aspp_mask)
+            return o
+
         G = 2
         x2 = None
         if isinstance(images, (tuple, list)):
@@ -222,9 +325,9 @@ class RGBXTransformer(nn.Module):                 # dual_segformer.py:228-446
                 side.wait_stream(main)
                 r.record_stream(side)
                 with torch.cuda.stream(side):
-                    outs.append(self.FFMs[s].run(store, r, B, Hc, Wc, training))
+                    outs.append(fuse(s, r, Hc, Wc))
             else:
-                outs.append(self.FFMs[s].run(store, r, B, Hc, Wc, training))
+                outs.append(fuse(s, r, Hc, Wc))
             grids.append((Hc, Wc))
             x = rn.view(G, B * Hc * Wc, C)
         if side is not None:
@@ -266,6 +369,25 @@ class mit_b5(RGBXTransformer):
 
 BACKBONES = {"mit_b0": mit_b0, "mit_b1": mit_b1, "mit_b2": mit_b2, "mit_b3": mit_b3, "mit_b4": mit_b4,
              "mit_b5": mit_b5}
+
+
+def _with_ef_aspp(name):
+    """``name`` + "_w_ef_aspp" (config.py's backbone names of dual_segformer_w_ef_aspp.py): the same encoder with the
+    eASPP neck on the stage-4 fused map.  Channels follow embed_dims, and mit_b1_w_ef_aspp is the real B1, as for the
+    plain backbones (models/builder.py's docstring)."""
+    spec = MIT_SPECS[name]
+
+    class Net(RGBXTransformer):
+        def __init__(self, fuse_cfg=None, frm="FRM", ffm="FFM", **kwargs):
+            super().__init__(**spec, drop_path_rate=0.1, frm=frm, ffm=ffm, aspp=True)
+
+    Net.__name__ = Net.__qualname__ = f"{name}_w_ef_aspp"
+    return Net
+
+
+for _name in list(MIT_SPECS):
+    MIT_SPECS[f"{_name}_w_ef_aspp"] = MIT_SPECS[_name]
+    BACKBONES[f"{_name}_w_ef_aspp"] = _with_ef_aspp(_name)
 
 
 def load_dualpath_model(model: nn.Module, model_file):

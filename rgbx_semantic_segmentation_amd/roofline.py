@@ -93,6 +93,7 @@ def _family_traffic(kernels, workload: str):
 # kernel-name -> family of the step census (the regexes of scripts/family_table.py; first match wins,
 # so the grouped weight-gradient launch is not counted as a tile GEMM)
 FAMILY_RE = (
+    ("easpp", r"easpp_"),        # before "frm": easpp_pool_bwd_kernel would match its pool_
     ("wgrad", r"gemm_grouped_kernel|reduce_grouped_kernel"),
     ("gemm", r"gemm_bf16_kernel|gemm_stream|gemm_multi|gemm_generic|splitk_reduce"),
     ("sra", r"sra_"),

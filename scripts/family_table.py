@@ -45,11 +45,13 @@ def work():
              "layernorm": "LayerNorm (fwd, bwd)", "adamw": "AdamW", "batchnorm": "BatchNorm (stats, fold, apply, bwd)",
              "frm": "FRM (pool, channel MLP, combine)", "ffm": "FFM context / cross attention",
              "ce": "upsample + CE", "bilinear": "bilinear (decoder fuse adjoint)", "im2col": "im2col / col2im",
-             "pe1": "stage-1 patch embed (direct conv fwd, wgrad)"}
+             "pe1": "stage-1 patch embed (direct conv fwd, wgrad)",
+             "easpp": "eASPP neck (dilated conv, concat, pooled branch, mask)"}
     return {names[k]: (v[0] or None, v[1] or None) for k, v in w.items()}
 
 
 FAMILIES = [
+    ("eASPP neck (dilated conv, concat, pooled branch, mask)", r"easpp_"),
     ("grouped wgrad GEMM + grouped reduce", r"gemm_grouped_kernel|reduce_grouped_kernel"),
     ("Mix-FFN bands", r"mixffn_"),
     ("GEMM fwd+dgrad (tile / streaming / k-group / multi / split-K)", r"gemm_bf16_kernel|gemm_stream|gemm_multi|gemm_generic|splitk_reduce"),

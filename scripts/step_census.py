@@ -68,6 +68,7 @@ for k, (n, t) in sorted(cat.items(), key=lambda x: -x[1][1])[:top]:
 
 # kernel families of the step (DESIGN.md per-family table)
 FAMILIES = [
+    ("eASPP neck (dilated conv, concat, pooled branch, mask)", r"^easpp_"),
     ("grouped wgrad + reduce (deferred weight gradients)", r"^(gemmk::)?gemm_grouped|^reduce_grouped"),
     ("GEMM (MFMA: linear / conv / decoder / attention projections)", r"^(gemmk::)?(gemm_|splitk_reduce)"),
     ("SRA attention (MFMA)", r"^sra_"),
