@@ -620,8 +620,8 @@ int cmx_frm_pool_fwd(const void* x, float* pooled, int* argmax, float* workspace
 int cmx_frm_pool_bwd(const float* dpooled_part, int nslice, int64_t slice_stride, const int* argmax, void* dx, int B,
                      int N, int C, int dtype, hipStream_t s) {
   const int V = dtype == 0 ? 4 : 8;
-  CMX_REQUIRE(C % V == 0 && C / V <= MAXCH * 64 && C <= 1024 && nslice > 0 && nslice <= PB_SL, CMX_ERR_SHAPE,
-              "frm_pool_bwd: C=%d nslice=%d", C, nslice);
+  CMX_REQUIRE(B > 0 && 2L * B <= 65535 && N > 0 && C > 0 && C % V == 0 && C / V <= MAXCH * 64 && C <= 1024 &&
+              nslice > 0 && nslice <= PB_SL, CMX_ERR_SHAPE, "frm_pool_bwd: B=%d N=%d C=%d nslice=%d", B, N, C, nslice);
   const int tpr = row_lanes(C, V);
   const int rpb = 256 / tpr;
   long nb = (N + rpb - 1) / rpb;
@@ -637,8 +637,9 @@ int cmx_frm_pool_bwd(const float* dpooled_part, int nslice, int64_t slice_stride
 
 int cmx_small_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int K, int Nout, int act,
                          hipStream_t s) {
-  CMX_REQUIRE(M > 0 && M <= MMAX && K % 4 == 0 && (long)M * K * 4 <= 64 * 1024 && ((uintptr_t)w & 15) == 0 &&
-              ((uintptr_t)x & 15) == 0, CMX_ERR_SHAPE, "small_linear_fwd: M=%d K=%d", M, K);
+  CMX_REQUIRE(M > 0 && M <= MMAX && K > 0 && K % 4 == 0 && (long)M * K * 4 <= 64 * 1024 && Nout > 0 &&
+              ((uintptr_t)w & 15) == 0 && ((uintptr_t)x & 15) == 0, CMX_ERR_SHAPE,
+              "small_linear_fwd: M=%d K=%d Nout=%d", M, K, Nout);
   const unsigned grid = cdiv(Nout, 4 * LIN_FPW);
   hipLaunchKernelGGL(linear_fwd_kernel, dim3(grid), dim3(256), (size_t)M * K * sizeof(float), s, x, w, b, y, M, K,
                      Nout, act);
@@ -652,8 +653,8 @@ size_t cmx_small_linear_bwd_workspace(int M, int K, int Nout) { return (size_t)N
 int cmx_small_linear_bwd(const float* dy_part, int dy_nslice, int64_t dy_slice_stride, int64_t dy_row_stride,
                          const float* y, const float* x, const float* w, float* dx_part, float* dw, float* db, int M,
                          int K, int Nout, int act, int accumulate, hipStream_t s) {
-  CMX_REQUIRE(M > 0 && M <= MMAX && dy_nslice > 0 && (Nout + NSLICE - 1) / NSLICE <= SLICE_MAX, CMX_ERR_SHAPE,
-              "small_linear_bwd: M=%d Nout=%d", M, Nout);
+  CMX_REQUIRE(M > 0 && M <= MMAX && K > 0 && Nout > 0 && dy_nslice > 0 && (Nout + NSLICE - 1) / NSLICE <= SLICE_MAX,
+              CMX_ERR_SHAPE, "small_linear_bwd: M=%d K=%d Nout=%d", M, K, Nout);
   hipLaunchKernelGGL(linear_bwd_kernel, dim3(cdiv(K, 64), NSLICE), dim3(256), 0, s, dy_part, dy_nslice,
                      (long)dy_slice_stride, (long)dy_row_stride, y, x, w, dx_part, dw, db, M, K, Nout, act,
                      accumulate);
@@ -663,7 +664,8 @@ int cmx_small_linear_bwd(const float* dy_part, int dy_nslice, int64_t dy_slice_s
 int cmx_frm_combine_fwd(const void* x, const float* cw, const void* h, const float* w2, const float* b2, float* sw,
                         void* out, int B, int N, int C, int dtype, hipStream_t s) {
   const int V = dtype == 0 ? 4 : 8;
-  CMX_REQUIRE(C % V == 0 && C / V <= MAXCH * 64, CMX_ERR_SHAPE, "frm_combine: C=%d", C);
+  CMX_REQUIRE(B > 0 && N > 0 && C > 0 && C % V == 0 && C / V <= MAXCH * 64, CMX_ERR_SHAPE,
+              "frm_combine: B=%d N=%d C=%d", B, N, C);
   const int tpr = row_lanes(C, V);
   const unsigned grid = rows_grid((long)B * N, 256 / tpr);
   CMX_DISPATCH(dtype, T, {
@@ -686,7 +688,8 @@ int cmx_frm_combine_bwd(const void* dout, const void* dout2, const void* x, cons
                         const float* w2, void* dx, void* dh, float* workspace, int B, int N, int C, int dtype,
                         hipStream_t s) {
   const int V = dtype == 0 ? 4 : 8;
-  CMX_REQUIRE(C % V == 0 && C / V <= MAXCH * 64, CMX_ERR_SHAPE, "frm_combine_bwd: C=%d", C);
+  CMX_REQUIRE(B > 0 && B <= 65535 && N > 0 && C > 0 && C % V == 0 && C / V <= MAXCH * 64, CMX_ERR_SHAPE,
+              "frm_combine_bwd: B=%d N=%d C=%d", B, N, C);
   const int nb = combine_nblk(N, C, V);
   const int tpr = row_lanes(C, V);
   float* pcw = workspace;
