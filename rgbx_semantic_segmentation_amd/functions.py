@@ -1848,6 +1848,52 @@ class UpsampleOhemF(Function):
         return _scale_adjoint(ctx, adj, dloss, out), None, None, None, None
 
 
+LOSS_CE = -1     # cmx_upsample_loss_scaled_fwd_adj's `kind` for plain CrossEntropyLoss
+LOSS_SCALES = (8, 16, 32)
+
+
+class UpsampleScaledLossF(Function):
+    """F.interpolate(logits, scale_factor=S, bilinear) + a per-pixel criterion at the scales of an FCN head
+    (S in 8, 16, 32: the stage-3 auxiliary head is x16, the FCN-32s decode head x32) fused as UpsampleLossF
+    is at x4 (cmx_upsample_loss_scaled_fwd_adj, include/cmx_fcn.h): one pass over the labels gives the loss
+    and the unscaled fp32 bilinear adjoint of the per-pixel gradient; the backward scales it by dloss /
+    normaliser (cmx_upsample_ce_bwd_scale).  spec None: plain CrossEntropyLoss; otherwise UpsampleLossF's
+    (kind, gamma, alpha, ce_scale, focal_scale).  weight as UpsampleLossF's.  S comes from dims: an (H, W)
+    that is not exactly (S h, S w) with S in the set raises NotImplementedError.  Without a backward to come
+    the same kernel runs and the adjoint is dropped."""
+
+    @staticmethod
+    def forward(ctx, logits, label, dims, ignore, spec, weight):
+        B, h, w, H, W, Kc = dims
+        S = H // h if h > 0 else 0
+        if S not in LOSS_SCALES or H != S * h or W != S * w:
+            raise NotImplementedError(f"fused upsample + loss at the scale of an FCN head: {h}x{w} -> {H}x{W} is not "
+                                      f"an exact scale in {LOSS_SCALES}")
+        kind, gamma, alpha, ce_scale, focal_scale = (LOSS_CE, 0.0, 0.0, 1.0, 0.0) if spec is None else spec
+        logits = _c(logits)
+        if weight is not None and (weight.device != logits.device or weight.dtype != torch.float32
+                                   or weight.numel() != Kc or not weight.is_contiguous()):
+            raise ValueError(f"class weight: {Kc} contiguous fp32 values on {logits.device} expected")
+        out = torch.empty(3, dtype=torch.float32, device=logits.device)
+        adj = torch.empty(B, h * w, Kc, dtype=torch.float32, device=logits.device)
+        ws = K._ws(K.query("cmx_upsample_loss_scaled_workspace", B, h, w, S), logits.device)
+        if K.refusable("cmx_upsample_loss_scaled_fwd_adj", (K.CMX_ERR_SHAPE,), logits, label, weight, adj, out, ws, B,
+                       h, w, S, Kc, ignore, int(kind), float(gamma), float(alpha), float(ce_scale), float(focal_scale),
+                       K.dtype_code(logits)) is K.REFUSED:
+            raise NotImplementedError(f"fused upsample + loss at the scale of an FCN head: {K.last_error()}")
+        if not ctx.needs_input_grad[0]:
+            return out[0]
+        ctx.save_for_backward(adj, out)
+        ctx.ldtype, ctx.lshape = logits.dtype, logits.shape
+        return out[0]             # a view of the kernel's result (no copy launch)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        adj, out = ctx.saved_tensors
+        dloss = _c(dloss.reshape(1).to(torch.float32))
+        return _scale_adjoint(ctx, adj, dloss, out), None, None, None, None, None
+
+
 def upsample_logits_nchw(logits, B, h, w, H, W, Kc):
     out = torch.empty(B, Kc, H, W, dtype=torch.float32, device=logits.device)
     K.call("cmx_bilinear_fwd_nchw_f32", _c(logits), out, B, h, w, H, W, Kc, K.dtype_code(logits))

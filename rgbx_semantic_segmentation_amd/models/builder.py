@@ -26,6 +26,14 @@ Differences by design:
     mask of the neck's Dropout keeps a step counter on the device; it is made by the first training forward, which
     must be an eager one (inside a graph capture it raises).
     ``forced_masks["aspp_dropout"]``: an optional (B, h, w, C4) 0/1 mask of the neck's Dropout for tests.
+  * ``cfg.decoder = "FCNHead"``: the reference's fallback branch (builder.py:186-189, FCN-32s: decoders.fcnhead.FCNHead
+    on the stage-4 map) under an explicit name; the other names of builder.py:154-189 stay refused.  ``cfg.aux_head``
+    (default False; ``cfg.aux_rate``, default 0.4): the auxiliary FCNHead on the stage-3 map of builder.py:167-170 beside
+    ANY decoder (the reference builds it only beside UPernet / DeepLabV3+); with a label the loss is main + aux_rate *
+    criterion(aux logits upsampled), in train and eval mode, and without one the head is not run.  A head that is not at
+    1/4 resolution takes its loss through functions.UpsampleScaledLossF: plain and class-weighted CrossEntropyLoss,
+    FocalLoss, FocalLoss2d and, for the decode head only, CE_Focal; Dice, DiceCE and OHEM with such a head, and CE_Focal
+    with aux_head (the reference would call the tuple), raise NotImplementedError at construction.
   * compute dtype: ``cfg.compute_dtype`` ("float32" | "bfloat16" | "float16"); defaults to
     float16 when ``cfg.use_mixed_precision`` (the reference's fp16 autocast switch,
     config.py:61, train.py:185-198: fp16 storage, fp32 accumulation, with dynamic loss scaling
@@ -46,6 +54,7 @@ from .. import kernels as K
 from ..params import ParamStore
 from .decoders import MLPDecoder, MLPDecoderpp
 from .decoders.MLPDecoder import DecoderHead
+from .decoders.fcnhead import FCNHead
 from .encoders.dual_segformer import BACKBONES, MIT_SPECS, load_dualpath_model
 
 logger = logging.getLogger("cmx")
@@ -78,7 +87,9 @@ def backward_segment(name: str) -> int:
 
 
 # cfg.decoder (builder.py:154-161 of the reference) -> decode head class
-DECODERS = {"MLPDecoder": MLPDecoder.DecoderHead, "MLPDecoderpp": MLPDecoderpp.DecoderHead}
+# "FCNHead": the reference's fallback branch (builder.py:186-189, FCN-32s on the stage-4 map) under an explicit name
+DECODERS = {"MLPDecoder": MLPDecoder.DecoderHead, "MLPDecoderpp": MLPDecoderpp.DecoderHead, "FCNHead": FCNHead}
+AUX_INDEX, AUX_RATE = 2, 0.4      # builder.py:168-169
 
 SUPPORTED_CRITERIA = ("nn.CrossEntropyLoss(reduction='mean'[, weight=w]), FocalLoss(reduction='mean', gamma == 0 or "
                       "gamma >= 1), FocalLoss2d(reduction='mean'[, weight=w]), DiceLoss(reduction='mean'), "
@@ -170,6 +181,24 @@ def _loss_plan(criterion):
     refuse(type(criterion).__name__)
 
 
+def check_head_criterion(criterion, decoder, aux_head):
+    """A head whose logits are not at 1/4 resolution (the FCNHead decode head at 1/32, the auxiliary head at 1/16)
+    takes its loss through UpsampleScaledLossF, which has the per-pixel criteria only: NotImplementedError naming the
+    reason for the others.  Needs no GPU (train.py calls it before any GPU work)."""
+    if decoder != "FCNHead" and not aux_head:
+        return
+    _, spec, _ = _loss_plan(criterion)
+    where = "decoder='FCNHead'" if decoder == "FCNHead" else "aux_head"
+    if isinstance(spec, (DiceSpec, OhemSpec)):
+        name = type(criterion).__name__
+        raise NotImplementedError(f"criterion {name} with {where}: the fused upsample + loss at x16 / x32 has plain and "
+                                  "class-weighted CrossEntropyLoss, FocalLoss, FocalLoss2d and (decode head only) "
+                                  f"CE_Focal; {name} exists at x4 only")
+    if aux_head and isinstance(criterion, (tuple, list)):
+        raise NotImplementedError("criterion CE_Focal with aux_head: the auxiliary loss is aux_rate * criterion(aux "
+                                  "logits, label), and the reference would call the tuple there (builder.py:250-251)")
+
+
 class EncoderDecoder(nn.Module):
     # the forward is one stream-ordered sequence of library launches with no host sync: callers
     # may capture it in a HIP graph (the evaluator does, per crop-batch shape)
@@ -183,7 +212,7 @@ class EncoderDecoder(nn.Module):
                                       "'_w_ef_aspp') is on the CMX hot path")
         decoder = _get(cfg, "decoder", "MLPDecoder")
         if decoder not in DECODERS:
-            raise NotImplementedError(f"decoder {decoder!r}: only {' and '.join(DECODERS)} are on the CMX hot path")
+            raise NotImplementedError(f"decoder {decoder!r}: only MLPDecoder and MLPDecoderpp are on the CMX hot path")
         # config.py:57-58 selects the rectify / fusion blocks (dual_segformer.py:316-329: 'FRM' / 'FFM'
         # the originals, any other value the improved IFRM / IFFM, as there)
         frm = _get(cfg, "feature_rectify_module", "FRM")
@@ -199,8 +228,23 @@ class EncoderDecoder(nn.Module):
         self.backbone = BACKBONES[backbone](norm_fuse=norm_layer, frm=frm, ffm=ffm)
         self.aux_head = None
         self.num_classes = int(_get(cfg, "num_classes", 40))
-        self.decode_head = DECODERS[decoder](in_channels=self.channels, num_classes=self.num_classes,
-                                             norm_layer=norm_layer, embed_dim=int(_get(cfg, "decoder_embed_dim", 512)))
+        aux = bool(_get(cfg, "aux_head", False))
+        check_head_criterion(criterion, decoder, aux)
+        if decoder == "FCNHead":           # builder.py:186-189: logits on the stage-4 grid
+            self.decode_head = FCNHead(in_channels=self.channels[-1], kernel_size=3, num_classes=self.num_classes,
+                                       norm_layer=norm_layer)
+            self.decode_head.out_index = 3
+        else:
+            self.decode_head = DECODERS[decoder](in_channels=self.channels, num_classes=self.num_classes,
+                                                 norm_layer=norm_layer,
+                                                 embed_dim=int(_get(cfg, "decoder_embed_dim", 512)))
+        if aux:
+            # the auxiliary head of builder.py:167-170 (there only beside UPernet / DeepLabV3+; cfg.aux_head is an
+            # extension that allows it beside every decoder here): FCNHead on the stage-3 map, logits at 1/16
+            self.aux_head = FCNHead(self.channels[AUX_INDEX], num_classes=self.num_classes, norm_layer=norm_layer)
+            self.aux_head.out_index = AUX_INDEX
+            self.aux_index = AUX_INDEX
+            self.aux_rate = float(_get(cfg, "aux_rate", AUX_RATE))
         self.bn_eps = float(_get(cfg, "bn_eps", 1e-3))
         self.bn_momentum = float(_get(cfg, "bn_momentum", 0.1))
         dt = _get(cfg, "compute_dtype", None)
@@ -224,7 +268,8 @@ class EncoderDecoder(nn.Module):
         if pretrained:
             logger.info("Loading pretrained model: %s", pretrained)
             load_dualpath_model(self.backbone, pretrained)
-        for m in self.decode_head.modules():
+        heads = [self.decode_head] + ([self.aux_head] if self.aux_head is not None else [])    # builder.py:204-210
+        for m in (m for head in heads for m in head.modules()):
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_in", nonlinearity="relu")
             elif isinstance(m, nn.BatchNorm2d):
@@ -323,7 +368,8 @@ class EncoderDecoder(nn.Module):
         return dp, d2
 
     # ------------------------------------------------------------------ forward
-    def _logits_lowres(self, rgb, modal_x):
+    def _logits_lowres(self, rgb, modal_x, with_aux=False):
+        """(low-res logits, their grid, (aux logits, their grid) or None)."""
         if self.store is None:
             raise RuntimeError("call model.cuda() first: EncoderDecoder has no CPU execution path")
         B, _, H, W = rgb.shape
@@ -348,21 +394,47 @@ class EncoderDecoder(nn.Module):
         # it the neck draws its mask on the device (eASPP.dropout_scale), inside a captured step too
         am = self.forced_masks.get("aspp_dropout") if (self.training and self.forced_masks is not None) else None
         feats, grids = self.backbone.run(self.store, images, B, H, W, self.training, dp, aspp_mask=am)
-        logits = self.decode_head.run(self.store, feats, grids, B, self.training, dscale=d2, group=group)
-        return logits, grids[0]
+        head = self.decode_head
+        if isinstance(head, FCNHead):      # one stage map; the logits live on that stage's grid
+            i = head.out_index
+            logits = head.run(self.store, feats[i], B, *grids[i], self.training, group=group)
+        else:
+            i = 0
+            logits = head.run(self.store, feats, grids, B, self.training, dscale=d2, group=group)
+        aux = None
+        if with_aux and self.aux_head is not None:
+            j = self.aux_index
+            aux = (self.aux_head.run(self.store, feats[j], B, *grids[j], self.training, group=group), grids[j])
+        return logits, grids[i], aux
 
     def encode_decode(self, rgb, modal_x):
-        logits, (h, w) = self._logits_lowres(rgb, modal_x)
+        # without a label the auxiliary head is not run: its result would be discarded (builder.py:240-253)
+        logits, (h, w), _ = self._logits_lowres(rgb, modal_x)
         B, _, H, W = rgb.shape
         return F.upsample_logits_nchw(logits, B, h, w, H, W, self.num_classes)
+
+    def _scaled_loss(self, logits, label, dims):
+        return F.UpsampleScaledLossF.apply(logits, label, dims, self.ignore_index, self._loss_spec, self._loss_weight)
 
     def forward(self, rgb, modal_x, label=None):
         if label is None:
             return self.encode_decode(rgb, modal_x)
-        logits, (h, w) = self._logits_lowres(rgb, modal_x)
+        logits, (h, w), aux = self._logits_lowres(rgb, modal_x, with_aux=True)
         B, _, H, W = rgb.shape
         label = label.to(device=logits.device, dtype=torch.int64).contiguous()
         dims = (B, h, w, H, W, self.num_classes)
+        loss = self._main_loss(logits, label, dims)
+        if aux is not None:
+            # builder.py:250-251, in train and eval mode alike: + aux_rate * criterion(aux logits upsampled, label)
+            alog, (ha, wa) = aux
+            aux_loss = self._scaled_loss(alog, label, (B, ha, wa, H, W, self.num_classes))
+            loss = torch.add(loss, aux_loss, alpha=self.aux_rate)      # one launch
+        return loss
+
+    def _main_loss(self, logits, label, dims):
+        B, h, w, H, W, _ = dims
+        if (H, W) != (4 * h, 4 * w) and isinstance(self.decode_head, FCNHead):
+            return self._scaled_loss(logits, label, dims)
         if self._loss_spec is None:        # plain CrossEntropyLoss
             return F.UpsampleCEF.apply(logits, label, dims, self.ignore_index)
         if isinstance(self._loss_spec, DiceSpec):

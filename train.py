@@ -35,13 +35,17 @@ logger = get_logger()
 
 CRITERIA = ("CrossEntropyLoss", "FocalLoss", "FocalLoss2d", "CE_Focal", "ProbOhemCrossEntropy2d")
 OPTIMIZERS = ("AdamW", "SGDM")
-DECODERS = ("MLPDecoder", "MLPDecoderpp")
+DECODERS = ("MLPDecoder", "MLPDecoderpp",
+            "FCNHead")       # the reference's fallback branch (builder.py:186-189), FCN-32s, under an explicit name
 
 
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--backbone", default="mit_b2")
     p.add_argument("--decoder", default="MLPDecoder", choices=DECODERS, help="config.decoder (config.py:51)")
+    p.add_argument("--aux-head", action="store_true",
+                   help="auxiliary FCNHead on the stage-3 map (builder.py:167-170): loss += aux-rate * criterion(aux)")
+    p.add_argument("--aux-rate", type=float, default=0.4, help="weight of the auxiliary loss (builder.py:169)")
     p.add_argument("--num-classes", type=int, default=40)
     p.add_argument("--height", type=int, default=480)
     p.add_argument("--width", type=int, default=640)
@@ -89,7 +93,17 @@ def build_parser():
 
 
 def build_criterion(args, background=255):
-    """The criterion object(s) train.py:70-88 builds for config.criterion; other names raise."""
+    """The criterion object(s) train.py:70-88 builds for config.criterion; other names raise, and so does a
+    criterion the chosen heads cannot take (--decoder FCNHead / --aux-head: the builder's message)."""
+    criterion = _build_criterion(args, background)
+    decoder, aux = getattr(args, "decoder", "MLPDecoder"), getattr(args, "aux_head", False)
+    if decoder == "FCNHead" or aux:
+        from rgbx_semantic_segmentation_amd.models.builder import check_head_criterion
+        check_head_criterion(criterion, decoder, aux)
+    return criterion
+
+
+def _build_criterion(args, background=255):
     from torch import nn
     from rgbx_semantic_segmentation_amd.utils.loss_opr import (DiceCELoss, DiceLoss, FocalLoss, FocalLoss2d,
                                                                ProbOhemCrossEntropy2d)
@@ -183,7 +197,7 @@ def main(argv=None):
         norm = torch.nn.SyncBatchNorm if engine.distributed else torch.nn.BatchNorm2d
         dtype, loss_scaling = resolve_precision(args)
         cfg = dict(backbone=args.backbone, decoder=args.decoder, num_classes=args.num_classes, compute_dtype=dtype,
-                   decoder_embed_dim=512)
+                   decoder_embed_dim=512, aux_head=args.aux_head, aux_rate=args.aux_rate)
         model = EncoderDecoder(cfg, criterion=criterion, norm_layer=norm).to(dev)
         sync = None
         if engine.distributed:
