@@ -99,6 +99,39 @@ template <> __device__ __forceinline__ f16x8 zfrag<f16>() {
   return __builtin_bit_cast(f16x8, make_uint4(0, 0, 0, 0));
 }
 
+// ---- whole 16-byte vectors as MFMA operands (the dilated convolutions of easpp.hip and aspp_conv.hip)
+// One MFMA k-step: each lane half supplies V = 16 B of consecutive k (8 x 16-bit: one 32x32x16; 4 x fp32:
+// four 32x32x2, whose k pairs are (j, V + j) -- any pairing works as long as A and B agree).
+template <typename T> constexpr int KV = 16 / (int)sizeof(T);
+template <typename T> using Raw = typename VecT<T>::raw;
+
+template <typename T>
+__device__ __forceinline__ f32x16 mma_step(const Raw<T>& a, const Raw<T>& b, f32x16 c) {
+  if constexpr (sizeof(T) == 4) {
+    c = MF<float>::mma(a.x, b.x, c);
+    c = MF<float>::mma(a.y, b.y, c);
+    c = MF<float>::mma(a.z, b.z, c);
+    return MF<float>::mma(a.w, b.w, c);
+  } else {
+    return MF<T>::mma(frag_bits<T>(a), frag_bits<T>(b), c);
+  }
+}
+
+template <typename T> __device__ __forceinline__ Raw<T> zero_raw() {
+  if constexpr (sizeof(T) == 4) return make_float4(0.f, 0.f, 0.f, 0.f);
+  else return make_uint4(0, 0, 0, 0);
+}
+
+// V elements gathered one by one (a strided k axis) -> the vector a contiguous load would have given
+template <typename T> __device__ __forceinline__ Raw<T> pack_raw(const T* e) {
+  if constexpr (sizeof(T) == 4) {
+    return make_float4(e[0], e[1], e[2], e[3]);
+  } else {
+    return make_uint4(e[0].x | ((uint32_t)e[1].x << 16), e[2].x | ((uint32_t)e[3].x << 16),
+                      e[4].x | ((uint32_t)e[5].x << 16), e[6].x | ((uint32_t)e[7].x << 16));
+  }
+}
+
 // 4 consecutive elements (16 B of fp32, 8 B of a 16-bit type)
 template <typename T>
 __device__ __forceinline__ void store4(T* p, const float* v) {

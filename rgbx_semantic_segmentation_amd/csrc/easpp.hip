@@ -29,38 +29,6 @@ struct Group3 {                           // the three branches' operands: a = p
   int rate[3];
 };
 
-// One MFMA k-step: each lane half supplies V = 16 B of consecutive k (8 x 16-bit: one 32x32x16; 4 x fp32:
-// four 32x32x2, whose k pairs are (j, V + j) -- any pairing works as long as A and B agree).
-template <typename T> constexpr int KV = 16 / (int)sizeof(T);
-template <typename T> using Raw = typename VecT<T>::raw;
-
-template <typename T>
-__device__ __forceinline__ f32x16 mma_step(const Raw<T>& a, const Raw<T>& b, f32x16 c) {
-  if constexpr (sizeof(T) == 4) {
-    c = MF<float>::mma(a.x, b.x, c);
-    c = MF<float>::mma(a.y, b.y, c);
-    c = MF<float>::mma(a.z, b.z, c);
-    return MF<float>::mma(a.w, b.w, c);
-  } else {
-    return MF<T>::mma(frag_bits<T>(a), frag_bits<T>(b), c);
-  }
-}
-
-template <typename T> __device__ __forceinline__ Raw<T> zero_raw() {
-  if constexpr (sizeof(T) == 4) return make_float4(0.f, 0.f, 0.f, 0.f);
-  else return make_uint4(0, 0, 0, 0);
-}
-
-// V elements gathered one by one (a strided k axis) -> the vector a contiguous load would have given
-template <typename T> __device__ __forceinline__ Raw<T> pack_raw(const T* e) {
-  if constexpr (sizeof(T) == 4) {
-    return make_float4(e[0], e[1], e[2], e[3]);
-  } else {
-    return make_uint4(e[0].x | ((uint32_t)e[1].x << 16), e[2].x | ((uint32_t)e[3].x << 16),
-                      e[4].x | ((uint32_t)e[5].x << 16), e[6].x | ((uint32_t)e[7].x << 16));
-  }
-}
-
 // forward: a = x, o = y;  DGRAD: a = dy, o = dx (taps mirrored, w read as (ci, co))
 template <typename T, bool DGRAD>
 __global__ __launch_bounds__(64) void easpp_conv_kernel(Group3 P, int B, int h, int w, long lda, long ldo) {

@@ -19,7 +19,18 @@ def easpp_macs(N, C) -> int:
     return N * (C * 448 + 9 * 9 * 64 * 64 + 3 * 64 * 256 + 1280 * C) + C * 256
 
 
-def forward_macs_per_image(backbone="mit_b2", H=480, W=640, K=40, E=512) -> int:
+def deeplabv3plus_macs(N1, C1, N4, C4, K) -> int:
+    """The DeepLabV3+ head (decoders/deeplabv3plus.py) on an N1-pixel, C1-channel stage-1 map and an N4-pixel,
+    C4-channel stage-4 map: ASPP's 1x1 conv and three dilated 3x3 convs C4 -> 256 (all 27 taps, as the reference runs
+    them), the pooled branch's 1x1 conv on one pixel, the 1280 -> 256 projection; the 3x3 C1 -> 48 projection, the 3x3
+    304 -> 256 conv and the classifier on the stage-1 grid."""
+    aspp = N4 * (C4 * 256 + 3 * 9 * C4 * 256 + 1280 * 256) + C4 * 256
+    return aspp + N1 * (9 * C1 * 48 + 9 * 304 * 256 + 256 * K)
+
+
+def forward_macs_per_image(backbone="mit_b2", H=480, W=640, K=40, E=512, decoder="MLPDecoder") -> int:
+    """decoder: "MLPDecoder" (the default; MLPDecoderpp's gate adds no counted op) or "DeepLabV3Plus" (without its
+    auxiliary head)."""
     dims, depths = MIT_SPECS[backbone]["embed_dims"], MIT_SPECS[backbone]["depths"]
     total = 0
     h, w = H, W
@@ -48,6 +59,8 @@ def forward_macs_per_image(backbone="mit_b2", H=480, W=640, K=40, E=512) -> int:
             total += easpp_macs(N, C)
         cin = C
     N1 = grids[0][0]
+    if decoder == "DeepLabV3Plus":
+        return total + deeplabv3plus_macs(N1, grids[0][1], grids[3][0], grids[3][1], K)
     total += sum(N * C * E for N, C in grids) + N1 * 4 * E * E + N1 * E * K
     return total
 

@@ -1434,6 +1434,59 @@ def easpp_dropout_scale(state, n, p, device):
     return scale
 
 
+# ---------------------------------------------------------------------------- DeepLabV3+ head
+class AsppConv3F(Function):
+    """ASPP.b1 .. b3's dilated 3x3 convolutions Cin -> Cout (deeplabv3plus.py:37-47) on ONE shared input x (B*h*w, Cin):
+    forward, input gradient and weight gradient each as one grouped launch (cmx_aspp_conv_*; the weight gradient folds
+    per-chunk partials in a second one when the rows are split).  The input gradient is the sum over the three
+    branches, accumulated in fp32 and rounded once: autograd would otherwise add three full maps.  Ws / Wgs: the
+    branches' tap-major weights and their fp32 gradient views."""
+
+    @staticmethod
+    def forward(ctx, geom, Ws, Wgs, a0, a1, a2, x):
+        B, h, w, rates = geom
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        ctx.save_for_backward(x)
+        ctx.meta = (geom, Ws, Wgs)
+        return K.aspp_conv_fwd(x, Ws, B, h, w, rates)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        x, = ctx.saved_tensors
+        (B, h, w, rates), Ws, Wgs = ctx.meta
+        dys = tuple(_c(d) for d in dys)
+        dx = K.aspp_conv_dgrad(dys, Ws, B, h, w, rates) if ctx.needs_input_grad[6] else None
+        K.aspp_conv_wgrad(dys, x, Wgs, B, h, w, rates)
+        return (None,) * 6 + (dx,)
+
+
+def aspp_conv3(store, convs, x, B, h, w):
+    """AsppConv3F on the three branches' nn.Conv2d modules ``convs`` (3x3, one dilation each, the same Cin -> Cout)."""
+    Ws = tuple(store.w(c.weight, stacked=False) for c in convs)
+    Wgs = tuple(store.g(c.weight, stacked=False) for c in convs)
+    geom = (B, h, w, tuple(int(c.dilation[0]) for c in convs))
+    return AsppConv3F.apply(geom, Ws, Wgs, *(c.weight for c in convs), x)
+
+
+class UpcatAcF(Function):
+    """torch.cat([F.interpolate(lo, (H, W), mode='bilinear', align_corners=True), skip], 1) (deeplabv3plus.py:32-33) on
+    token rows, one launch each way: lo (B*h*w, C), skip (B*H*W, Cs) -> (B*H*W, C + Cs)."""
+
+    @staticmethod
+    def forward(ctx, lo, skip, dims):
+        B, h, w, H, W = dims
+        lo, skip = _c(lo), _c(skip)
+        ctx.meta = (dims, lo.shape[-1], skip.shape[-1])
+        return K.upcat_ac_fwd(lo, skip, B, h, w, H, W)
+
+    @staticmethod
+    def backward(ctx, dcat):
+        (B, h, w, H, W), C, Cs = ctx.meta
+        dlo, dskip = K.upcat_ac_bwd(_c(dcat), B, h, w, H, W, C, Cs)
+        return dlo, dskip, None
+
+
 # ---------------------------------------------------------------------------- decoder fuse
 def _adjoint_to(dZ, B, H1, W1, h, w, E):
     """up^T dZ: the bilinear adjoint of the (h, w) -> (H1, W1) upsample, (B, h*w, E) in dZ's

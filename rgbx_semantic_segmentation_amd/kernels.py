@@ -485,3 +485,47 @@ def easpp_conv_wgrad(dys, xs, Wgs, B, h, w, rates):
     ws = _ws(query("cmx_easpp_conv_wgrad_workspace", B, h, w), xs[0].device)
     call("cmx_easpp_conv_wgrad", *dys, *xs, *Wgs, ws, B, h, w, xs[0].shape[-1], *rates, dys[0].stride(0),
          xs[0].stride(0), dtype_code(xs[0]))
+
+
+# ------------------------------------------------------------------------------ DeepLabV3+ head (include/cmx_deeplab.h)
+def aspp_conv_fwd(x, Ws, B, h, w, rates):
+    """ASPP's three dilated 3x3 convolutions of ONE input x (B*h*w, Cin at any row stride) with the tap-major weights
+    Ws[g] (Cout, 3, 3, Cin): the three outputs (B*h*w, Cout) of one launch (cmx_aspp_conv_fwd)."""
+    Cout, Cin = Ws[0].shape[0], Ws[0].shape[-1]
+    ys = tuple(torch.empty(x.shape[0], Cout, dtype=x.dtype, device=x.device) for _ in range(3))
+    call("cmx_aspp_conv_fwd", x, *Ws, *ys, B, h, w, Cin, Cout, *rates, x.stride(0), Cout, dtype_code(x))
+    return ys
+
+
+def aspp_conv_dgrad(dys, Ws, B, h, w, rates):
+    """dx (B*h*w, Cin): the SUM of the three branches' input gradients, rounded once (cmx_aspp_conv_dgrad); the three
+    dys[g] (B*h*w, Cout) share one row stride."""
+    Cout, Cin = Ws[0].shape[0], Ws[0].shape[-1]
+    dx = torch.empty(dys[0].shape[0], Cin, dtype=dys[0].dtype, device=dys[0].device)
+    call("cmx_aspp_conv_dgrad", *dys, *Ws, dx, B, h, w, Cin, Cout, *rates, dys[0].stride(0), Cin, dtype_code(dx))
+    return dx
+
+
+def aspp_conv_wgrad(dys, x, Wgs, B, h, w, rates):
+    """Wgs[g] (fp32 (Cout, 3, 3, Cin) views of the gradient buffer) = the branches' weight gradients (overwritten)."""
+    Cout, Cin = Wgs[0].shape[0], Wgs[0].shape[-1]
+    ws = _ws(query("cmx_aspp_conv_wgrad_workspace", B, h, w, Cin, Cout), x.device)
+    call("cmx_aspp_conv_wgrad", *dys, x, *Wgs, ws, B, h, w, Cin, Cout, *rates, dys[0].stride(0), x.stride(0),
+         dtype_code(x))
+
+
+def upcat_ac_fwd(lo, skip, B, h, w, H, W):
+    """cat (B*H*W, C + Cs) = [bilinear align_corners=True upsample of lo (B*h*w, C) | skip (B*H*W, Cs)], contiguous
+    operands (cmx_upcat_ac_fwd)."""
+    C, Cs = lo.shape[-1], skip.shape[-1]
+    cat = torch.empty(B * H * W, C + Cs, dtype=lo.dtype, device=lo.device)
+    call("cmx_upcat_ac_fwd", lo, skip, cat, B, h, w, H, W, C, Cs, dtype_code(lo))
+    return cat
+
+
+def upcat_ac_bwd(dcat, B, h, w, H, W, C, Cs):
+    """(dlo (B*h*w, C), dskip (B*H*W, Cs)) of upcat_ac_fwd, one launch (cmx_upcat_ac_bwd)."""
+    dlo = torch.empty(B * h * w, C, dtype=dcat.dtype, device=dcat.device)
+    dskip = torch.empty(B * H * W, Cs, dtype=dcat.dtype, device=dcat.device)
+    call("cmx_upcat_ac_bwd", dcat, dlo, dskip, B, h, w, H, W, C, Cs, dtype_code(dcat))
+    return dlo, dskip

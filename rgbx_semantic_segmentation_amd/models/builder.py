@@ -34,6 +34,14 @@ Differences by design:
     1/4 resolution takes its loss through functions.UpsampleScaledLossF: plain and class-weighted CrossEntropyLoss,
     FocalLoss, FocalLoss2d and, for the decode head only, CE_Focal; Dice, DiceCE and OHEM with such a head, and CE_Focal
     with aux_head (the reference would call the tuple), raise NotImplementedError at construction.
+  * ``cfg.decoder = "DeepLabV3Plus"``: the reference's ``deeplabv3+`` branch (builder.py:172-179,
+    decoders.deeplabv3plus.DeepLabV3Plus) under its class name; the reference's own spelling stays refused, as do
+    ``UPernet`` and ``mask2former``.  Its logits are at 1/4 resolution, so every criterion above applies to it.  As in the
+    reference the auxiliary FCNHead is built beside it BY DEFAULT (``cfg.aux_head = False`` switches it off; Dice, DiceCE,
+    OHEM and CE_Focal need that).  Training with one image per batch raises ValueError and a batch is at most 8 images
+    per GPU (the pooled ASPP branch, as for the eASPP neck); the head's two elementwise Dropouts keep device step counters
+    made by the first, eager training forward.  ``forced_masks["dlv3_aspp_dropout"]`` (B, h4, w4, 256) and
+    ``forced_masks["dlv3_block_dropout"]`` (B, h1, w1, 256): optional 0/1 masks of those Dropouts for tests.
   * compute dtype: ``cfg.compute_dtype`` ("float32" | "bfloat16" | "float16"); defaults to
     float16 when ``cfg.use_mixed_precision`` (the reference's fp16 autocast switch,
     config.py:61, train.py:185-198: fp16 storage, fp32 accumulation, with dynamic loss scaling
@@ -54,6 +62,7 @@ from .. import kernels as K
 from ..params import ParamStore
 from .decoders import MLPDecoder, MLPDecoderpp
 from .decoders.MLPDecoder import DecoderHead
+from .decoders.deeplabv3plus import DeepLabV3Plus
 from .decoders.fcnhead import FCNHead
 from .encoders.dual_segformer import BACKBONES, MIT_SPECS, load_dualpath_model
 
@@ -88,7 +97,10 @@ def backward_segment(name: str) -> int:
 
 # cfg.decoder (builder.py:154-161 of the reference) -> decode head class
 # "FCNHead": the reference's fallback branch (builder.py:186-189, FCN-32s on the stage-4 map) under an explicit name
-DECODERS = {"MLPDecoder": MLPDecoder.DecoderHead, "MLPDecoderpp": MLPDecoderpp.DecoderHead, "FCNHead": FCNHead}
+# "DeepLabV3Plus": the reference's 'deeplabv3+' branch (builder.py:172-179) under its class name
+DECODERS = {"MLPDecoder": MLPDecoder.DecoderHead, "MLPDecoderpp": MLPDecoderpp.DecoderHead, "FCNHead": FCNHead,
+            "DeepLabV3Plus": DeepLabV3Plus}
+AUX_BY_DEFAULT = ("DeepLabV3Plus",)   # builder.py:172-179 builds the auxiliary head beside this decoder
 AUX_INDEX, AUX_RATE = 2, 0.4      # builder.py:168-169
 
 SUPPORTED_CRITERIA = ("nn.CrossEntropyLoss(reduction='mean'[, weight=w]), FocalLoss(reduction='mean', gamma == 0 or "
@@ -181,10 +193,16 @@ def _loss_plan(criterion):
     refuse(type(criterion).__name__)
 
 
+def effective_aux(decoder, aux_head) -> bool:
+    """Whether the auxiliary head is built: ``aux_head`` as configured (None: not set), else the decoder's default."""
+    return bool(aux_head) if aux_head is not None else decoder in AUX_BY_DEFAULT
+
+
 def check_head_criterion(criterion, decoder, aux_head):
     """A head whose logits are not at 1/4 resolution (the FCNHead decode head at 1/32, the auxiliary head at 1/16)
     takes its loss through UpsampleScaledLossF, which has the per-pixel criteria only: NotImplementedError naming the
-    reason for the others.  Needs no GPU (train.py calls it before any GPU work)."""
+    reason for the others.  ``aux_head``: the effective setting (effective_aux).  Needs no GPU (train.py calls it before
+    any GPU work)."""
     if decoder != "FCNHead" and not aux_head:
         return
     _, spec, _ = _loss_plan(criterion)
@@ -193,10 +211,13 @@ def check_head_criterion(criterion, decoder, aux_head):
         name = type(criterion).__name__
         raise NotImplementedError(f"criterion {name} with {where}: the fused upsample + loss at x16 / x32 has plain and "
                                   "class-weighted CrossEntropyLoss, FocalLoss, FocalLoss2d and (decode head only) "
-                                  f"CE_Focal; {name} exists at x4 only")
+                                  f"CE_Focal; {name} exists at x4 only" +
+                                  (" (the decode head is at x4: use it on the main head alone, or set aux_head=False)"
+                                   if decoder != "FCNHead" else ""))
     if aux_head and isinstance(criterion, (tuple, list)):
         raise NotImplementedError("criterion CE_Focal with aux_head: the auxiliary loss is aux_rate * criterion(aux "
-                                  "logits, label), and the reference would call the tuple there (builder.py:250-251)")
+                                  "logits, label), and the reference would call the tuple there (builder.py:250-251); "
+                                  "use another criterion, or set aux_head=False")
 
 
 class EncoderDecoder(nn.Module):
@@ -212,7 +233,9 @@ class EncoderDecoder(nn.Module):
                                       "'_w_ef_aspp') is on the CMX hot path")
         decoder = _get(cfg, "decoder", "MLPDecoder")
         if decoder not in DECODERS:
-            raise NotImplementedError(f"decoder {decoder!r}: only MLPDecoder and MLPDecoderpp are on the CMX hot path")
+            raise NotImplementedError(f"decoder {decoder!r}: only MLPDecoder and MLPDecoderpp are on the CMX hot path" +
+                                      (" (the DeepLabV3+ head is selected by its class name, decoder='DeepLabV3Plus')"
+                                       if decoder == "deeplabv3+" else ""))
         # config.py:57-58 selects the rectify / fusion blocks (dual_segformer.py:316-329: 'FRM' / 'FFM'
         # the originals, any other value the improved IFRM / IFFM, as there)
         frm = _get(cfg, "feature_rectify_module", "FRM")
@@ -228,19 +251,23 @@ class EncoderDecoder(nn.Module):
         self.backbone = BACKBONES[backbone](norm_fuse=norm_layer, frm=frm, ffm=ffm)
         self.aux_head = None
         self.num_classes = int(_get(cfg, "num_classes", 40))
-        aux = bool(_get(cfg, "aux_head", False))
+        aux = effective_aux(decoder, _get(cfg, "aux_head", None))
         check_head_criterion(criterion, decoder, aux)
         if decoder == "FCNHead":           # builder.py:186-189: logits on the stage-4 grid
             self.decode_head = FCNHead(in_channels=self.channels[-1], kernel_size=3, num_classes=self.num_classes,
                                        norm_layer=norm_layer)
             self.decode_head.out_index = 3
+        elif decoder == "DeepLabV3Plus":   # builder.py:172-179: the reference's constructor, logits on the stage-1 grid
+            self.decode_head = DeepLabV3Plus(in_channels=self.channels, num_classes=self.num_classes,
+                                             norm_layer=norm_layer)
         else:
             self.decode_head = DECODERS[decoder](in_channels=self.channels, num_classes=self.num_classes,
                                                  norm_layer=norm_layer,
                                                  embed_dim=int(_get(cfg, "decoder_embed_dim", 512)))
         if aux:
-            # the auxiliary head of builder.py:167-170 (there only beside UPernet / DeepLabV3+; cfg.aux_head is an
-            # extension that allows it beside every decoder here): FCNHead on the stage-3 map, logits at 1/16
+            # the auxiliary head of builder.py:167-170 (there only beside UPernet / DeepLabV3+, where it is the default
+            # here too; cfg.aux_head is an extension that allows it beside every decoder): FCNHead on the stage-3 map,
+            # logits at 1/16
             self.aux_head = FCNHead(self.channels[AUX_INDEX], num_classes=self.num_classes, norm_layer=norm_layer)
             self.aux_head.out_index = AUX_INDEX
             self.aux_index = AUX_INDEX
@@ -400,6 +427,8 @@ class EncoderDecoder(nn.Module):
             logits = head.run(self.store, feats[i], B, *grids[i], self.training, group=group)
         else:
             i = 0
+            if isinstance(head, DeepLabV3Plus):     # its two elementwise Dropouts take their forced masks from here
+                head.forced_masks = self.forced_masks if self.training else None
             logits = head.run(self.store, feats, grids, B, self.training, dscale=d2, group=group)
         aux = None
         if with_aux and self.aux_head is not None:

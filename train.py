@@ -36,7 +36,8 @@ logger = get_logger()
 CRITERIA = ("CrossEntropyLoss", "FocalLoss", "FocalLoss2d", "CE_Focal", "ProbOhemCrossEntropy2d")
 OPTIMIZERS = ("AdamW", "SGDM")
 DECODERS = ("MLPDecoder", "MLPDecoderpp",
-            "FCNHead")       # the reference's fallback branch (builder.py:186-189), FCN-32s, under an explicit name
+            "FCNHead",       # the reference's fallback branch (builder.py:186-189), FCN-32s, under an explicit name
+            "DeepLabV3Plus")  # the reference's 'deeplabv3+' branch (builder.py:172-179) under its class name
 
 
 def build_parser():
@@ -45,6 +46,9 @@ def build_parser():
     p.add_argument("--decoder", default="MLPDecoder", choices=DECODERS, help="config.decoder (config.py:51)")
     p.add_argument("--aux-head", action="store_true",
                    help="auxiliary FCNHead on the stage-3 map (builder.py:167-170): loss += aux-rate * criterion(aux)")
+    p.add_argument("--no-aux-head", action="store_true",
+                   help="--decoder DeepLabV3Plus builds the auxiliary head by default, as the reference does "
+                        "(builder.py:172-179): leave it out")
     p.add_argument("--aux-rate", type=float, default=0.4, help="weight of the auxiliary loss (builder.py:169)")
     p.add_argument("--num-classes", type=int, default=40)
     p.add_argument("--height", type=int, default=480)
@@ -92,11 +96,18 @@ def build_parser():
     return p
 
 
+def effective_aux_head(args) -> bool:
+    """--aux-head, or the default of --decoder DeepLabV3Plus unless --no-aux-head."""
+    return bool(getattr(args, "aux_head", False)) or (getattr(args, "decoder", "MLPDecoder") == "DeepLabV3Plus"
+                                                      and not getattr(args, "no_aux_head", False))
+
+
 def build_criterion(args, background=255):
     """The criterion object(s) train.py:70-88 builds for config.criterion; other names raise, and so does a
-    criterion the chosen heads cannot take (--decoder FCNHead / --aux-head: the builder's message)."""
+    criterion the chosen heads cannot take (--decoder FCNHead / --aux-head, which --decoder DeepLabV3Plus implies
+    unless --no-aux-head: the builder's message)."""
     criterion = _build_criterion(args, background)
-    decoder, aux = getattr(args, "decoder", "MLPDecoder"), getattr(args, "aux_head", False)
+    decoder, aux = getattr(args, "decoder", "MLPDecoder"), effective_aux_head(args)
     if decoder == "FCNHead" or aux:
         from rgbx_semantic_segmentation_amd.models.builder import check_head_criterion
         check_head_criterion(criterion, decoder, aux)
@@ -197,7 +208,7 @@ def main(argv=None):
         norm = torch.nn.SyncBatchNorm if engine.distributed else torch.nn.BatchNorm2d
         dtype, loss_scaling = resolve_precision(args)
         cfg = dict(backbone=args.backbone, decoder=args.decoder, num_classes=args.num_classes, compute_dtype=dtype,
-                   decoder_embed_dim=512, aux_head=args.aux_head, aux_rate=args.aux_rate)
+                   decoder_embed_dim=512, aux_head=effective_aux_head(args), aux_rate=args.aux_rate)
         model = EncoderDecoder(cfg, criterion=criterion, norm_layer=norm).to(dev)
         sync = None
         if engine.distributed:
