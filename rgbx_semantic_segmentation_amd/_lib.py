@@ -7,7 +7,8 @@ same way into a table of its own, ``OHEM_SIGNATURES``; its entry points are call
 ``include/cmx_easpp.h`` (part 3: the eASPP neck of the ``mit_b*_w_ef_aspp`` backbones) likewise, into
 ``EASPP_SIGNATURES``.  ``include/cmx_fcn.h`` (part 4: the fused upsample + loss at the scales of an FCN head)
 likewise, into ``FCN_SIGNATURES``.  ``include/cmx_deeplab.h`` (part 5: the DeepLabV3+ head's wide dilated convolution and
-align-corners upsample + concat) likewise, into ``DEEPLAB_SIGNATURES``.
+align-corners upsample + concat) likewise, into ``DEEPLAB_SIGNATURES``.  ``include/cmx_mlp.h`` (part 6: the Mix-FFN of stages
+1-2 with its Linears inside the depthwise kernels) likewise, into ``MLP_SIGNATURES``.
 
 ``call`` / ``try_call`` / ``query`` / ``refusable`` take an entry point's name and its arguments in
 header order; ``marshal`` converts them by the kind the header declares for each parameter:
@@ -40,6 +41,7 @@ OHEM_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_ohem.h"), os.path
 EASPP_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_easpp.h"), os.path.join(_HERE, "cmx_easpp.h")]
 FCN_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_fcn.h"), os.path.join(_HERE, "cmx_fcn.h")]
 DEEPLAB_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_deeplab.h"), os.path.join(_HERE, "cmx_deeplab.h")]
+MLP_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_mlp.h"), os.path.join(_HERE, "cmx_mlp.h")]
 
 
 class CMXError(RuntimeError):
@@ -118,16 +120,17 @@ def _load():
     easpp = parse_header(next(p for p in EASPP_HEADER_PATHS if os.path.exists(p)))
     fcn = parse_header(next(p for p in FCN_HEADER_PATHS if os.path.exists(p)))
     deeplab = parse_header(next(p for p in DEEPLAB_HEADER_PATHS if os.path.exists(p)))
-    for table in (sigs, ohem, easpp, fcn, deeplab):
+    mlp = parse_header(next(p for p in MLP_HEADER_PATHS if os.path.exists(p)))
+    for table in (sigs, ohem, easpp, fcn, deeplab, mlp):
         for name, (rt, argt) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argt
             fn.restype = rt
             assert STREAM not in table[name].kinds[:-1], f"{name}: hipStream_t must be the last parameter"
-    return lib, sigs, ohem, easpp, fcn, deeplab
+    return lib, sigs, ohem, easpp, fcn, deeplab, mlp
 
 
-LIB, SIGNATURES, OHEM_SIGNATURES, EASPP_SIGNATURES, FCN_SIGNATURES, DEEPLAB_SIGNATURES = _load()
+LIB, SIGNATURES, OHEM_SIGNATURES, EASPP_SIGNATURES, FCN_SIGNATURES, DEEPLAB_SIGNATURES, MLP_SIGNATURES = _load()
 
 
 def last_error() -> str:
@@ -156,7 +159,7 @@ def _scalar_arg(a):
 _BOUND = {name: (getattr(LIB, name), tuple(_pointer_arg if k == POINTER else _scalar_arg for k in sig.kinds),
                  sig.kinds[-1:] == (STREAM,))
           for name, sig in {**SIGNATURES, **OHEM_SIGNATURES, **EASPP_SIGNATURES, **FCN_SIGNATURES,
-                            **DEEPLAB_SIGNATURES}.items()}
+                            **DEEPLAB_SIGNATURES, **MLP_SIGNATURES}.items()}
 
 
 def marshal(name: str, args: tuple) -> tuple:

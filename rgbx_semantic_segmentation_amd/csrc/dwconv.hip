@@ -20,6 +20,8 @@
 // (That strip path now serves only channel counts that are not multiples of 32; see the
 // LDS-tiled path below for every layer of B0 / B2.)
 #include "cmx_common.h"
+#include "cmx_mfma.h"
+#include "../../include/cmx_mlp.h"  // compiler-checks the Mix-FFN entry points below against the ABI header
 
 namespace {
 constexpr int RXF = 4;           // output pixels per strip along x (forward / transposed pass)
@@ -403,8 +405,9 @@ __device__ __forceinline__ void v4_store(T* p, const cmx_f2 (&o)[2]) {
   if constexpr (sizeof(T) == 2) *reinterpret_cast<uint2*>(p) = make_uint2(pack2<T>(o[0].x, o[0].y), pack2<T>(o[1].x, o[1].y));
   else *reinterpret_cast<float4*>(p) = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
 }
-// stage a (RY x RX)-pixel region into a pixel-major image img[px][CB]; zeros outside the image
-template <typename T, int CB, int RY_, int RX_>
+// stage a (RY x RX)-pixel region into a pixel-major image img[px][PITCH] (PITCH >= CB elements per
+// pixel, a multiple of 8); zeros outside the image
+template <typename T, int CB, int RY_, int RX_, int PITCH = CB>
 __device__ __forceinline__ void stage_region_pm(const T* __restrict__ base, T* img, int y0, int x0, int H, int W, int C) {
   constexpr int NCG = CB / 8, NPX = RY_ * RX_;
   constexpr int ITER = (NCG * NPX + 255) / 256;
@@ -420,7 +423,57 @@ __device__ __forceinline__ void stage_region_pm(const T* __restrict__ base, T* i
 #pragma unroll
   for (int k = 0; k < ITER; ++k) {
     const int it = threadIdx.x + k * 256;
-    if (it < NCG * NPX) v8_store<T>(img + it * 8, v[k]);
+    if (it < NCG * NPX) v8_store<T>(img + (it / NCG) * PITCH + (it % NCG) * 8, v[k]);
+  }
+}
+
+// One thread's column of the forward tile (CB = 64: 16 channel quads, so the 16 pixel slots of a
+// block-wide step are the TX2 columns).  hp = the thread's 4 channels of halo pixel (row 0, column
+// c) in an LDS image of PITCH elements per pixel; rows 0 .. TY2-1 of inner column c go to out
+// (and act'(z) to gprime) at element offset o, o + ostep, ...  The 3 x 3 window of unpacked taps
+// slides down the column in registers: each row fetches and unpacks only its three new bottom
+// taps; the rows rotate by renaming, the loop being fully unrolled.  COPY_IN: the LDS image was
+// computed in this block, and the column's inner input pixels are also stored to hin.
+template <typename T, int ACT, bool FLIP, int PITCH, bool COPY_IN>
+__device__ __forceinline__ void dw2_fwd_column(const T* hp, const cmx_f2 (&wr)[2][9], const cmx_f2 (&bias)[2],
+                                               T* __restrict__ out, T* __restrict__ gprime, T* __restrict__ hin,
+                                               long o, long ostep, int nr) {
+  cmx_f2 win[3][3][2];                              // [image row % 3][column c .. c+2][pair]
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    v4_unpack<T>(v4_load<T>(hp + j * PITCH), win[0][j]);
+    v4_unpack<T>(v4_load<T>(hp + (EX + j) * PITCH), win[1][j]);
+  }
+#pragma unroll
+  for (int r = 0; r < TY2; ++r) {
+    if (r < nr) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        v4_unpack<T>(v4_load<T>(hp + ((r + 2) * EX + j) * PITCH), win[(r + 2) % 3][j]);
+      }
+      if constexpr (COPY_IN) {
+        *reinterpret_cast<V4<T>*>(hin + o) = v4_load<T>(hp + ((r + 1) * EX + 1) * PITCH);
+      }
+      cmx_f2 acc[2] = {bias[0], bias[1]};
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const int tap = FLIP ? 8 - (i * 3 + j) : i * 3 + j;
+#pragma unroll
+          for (int u = 0; u < 2; ++u) acc[u] = pk_fma(wr[u][tap], win[(r + i) % 3][j][u], acc[u]);
+        }
+      if (gprime) {            // act'(z), saved so the backward needs no conv recompute
+        cmx_f2 gd[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) gd[u] = act2_grad<ACT>(acc[u]);
+        v4_store<T>(gprime + o, gd);
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) acc[u] = act2_fwd<ACT>(acc[u]);
+      v4_store<T>(out + o, acc);
+      o += ostep;
+    }
   }
 }
 
@@ -447,50 +500,13 @@ __global__ __launch_bounds__(256) void dw2_fwd_kernel(const T* __restrict__ h, c
   }
   const T* hc = hs + cq * 4;
   if constexpr (PPI == TX2) {
-    // A thread's pixels are rows 0 .. TY2-1 of ONE tile column (c = pl): the 3 x 3 window of
-    // unpacked taps slides down it in registers.  Each row fetches and unpacks only its three
-    // new bottom taps; the rows rotate by renaming, the loop being fully unrolled.  Every
+    // A thread's pixels are rows 0 .. TY2-1 of ONE tile column (c = pl): dw2_fwd_column.  Every
     // output keeps the tap order of the loop below.
     const int x = t.tx0 + pl;
     const int nr = H - t.ty0;                       // rows of this tile inside the image (block-uniform)
     if (x >= W) return;                             // no barrier after this point
-    const T* hp = hc + pl * CB;
-    cmx_f2 win[3][3][2];                            // [image row % 3][column c .. c+2][pair]
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      v4_unpack<T>(v4_load<T>(hp + j * CB), win[0][j]);
-      v4_unpack<T>(v4_load<T>(hp + (EX + j) * CB), win[1][j]);
-    }
-    long o = ibase + ((long)t.ty0 * W + x) * C + cq * 4;
-    const long ostep = (long)W * C;
-#pragma unroll
-    for (int r = 0; r < TY2; ++r) {
-      if (r < nr) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          v4_unpack<T>(v4_load<T>(hp + ((r + 2) * EX + j) * CB), win[(r + 2) % 3][j]);
-        }
-        cmx_f2 acc[2] = {bias[0], bias[1]};
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            const int tap = FLIP ? 8 - (i * 3 + j) : i * 3 + j;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) acc[u] = pk_fma(wr[u][tap], win[(r + i) % 3][j][u], acc[u]);
-          }
-        if (gprime) {            // act'(z), saved so the backward needs no conv recompute
-          cmx_f2 gd[2];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) gd[u] = act2_grad<ACT>(acc[u]);
-          v4_store<T>(gprime + o, gd);
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) acc[u] = act2_fwd<ACT>(acc[u]);
-        v4_store<T>(out + o, acc);
-        o += ostep;
-      }
-    }
+    dw2_fwd_column<T, ACT, FLIP, CB, false>(hc + pl * CB, wr, bias, out, gprime, nullptr,
+                                            ibase + ((long)t.ty0 * W + x) * C + cq * 4, (long)W * C, nr);
   } else {
     for (int it = pl; it < TY2 * TX2; it += PPI) {
       const int r = it / TX2, c = it % TX2;
@@ -519,6 +535,128 @@ __global__ __launch_bounds__(256) void dw2_fwd_kernel(const T* __restrict__ h, c
       v4_store<T>(out + o, acc);
     }
   }
+}
+
+// ---------------------------------------------------------------------------- Mix-FFN fusion
+// Stages 1-2 (C = 64 / 128): the Linear on either side of the depthwise conv has K = C only, so
+// the conv kernels compute its product for their own tile (+ halo) with MFMA instead of reading
+// it back from memory.  Pixels go in chunks of 32 (the MFMA's 32 columns) against the block's 64
+// hidden channels (two 32-row halves): wave w takes half w & 1 of chunks w >> 1, w >> 1 + 2, ...
+// Per element the arithmetic is that of the GEMM kernels (gemm_kernels.h): the weight fragment
+// is the MFMA's A operand, one fp32 accumulator walks the k16 steps in ascending order, lane
+// half h carries k = 16 s + 8 h .. + 7, and the result is rounded to the storage type where the
+// GEMM's epilogue rounds it -- so the fused kernels give the bits of the launches they replace.
+// Computed LDS images have a pitch of CB + 8 elements per pixel: the 32 pixels of a chunk (one
+// per lane) then spread over the banks instead of sharing one.
+constexpr int MLP_CB = 64, MLP_PM = MLP_CB + 8;
+
+// A wave's NCW chunks as ONE stream of k16 steps: chunk j's product is
+//   acc = sum_k Wfrag(row = hidden channel, k) * act(pixel = this lane's r, k),   KC = C,
+// its activation rows starting at a + off[j] (this lane's pixel and k half).  The 16-B fragment
+// loads run D steps ahead of the MFMAs in a register ring, across chunk boundaries, so the wave
+// waits for memory once, not once per chunk.  epi(j, acc) consumes chunk j's accumulator.
+template <typename T, int KC, int NCW, int D, typename Epi>
+__device__ __forceinline__ void mlp_chunk_stream(const typename MF<T>::frag (&fw)[KC / 16], const T* __restrict__ a,
+                                                 const int (&off)[NCW], Epi epi) {
+  constexpr int KS = KC / 16, NS = NCW * KS;
+  static_assert(D <= NS, "ring deeper than the stream");
+  typename MF<T>::frag ring[D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) ring[i] = MF<T>::load(a + off[i / KS] + 16 * (i % KS));
+  f32x16 acc = zero16();
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const typename MF<T>::frag f = ring[i % D];
+    if (i + D < NS) ring[i % D] = MF<T>::load(a + off[(i + D) / KS] + 16 * ((i + D) % KS));
+    acc = MF<T>::mma(fw[i % KS], f, acc);
+    if (i % KS == KS - 1) {
+      epi(i / KS, acc);
+      acc = zero16();
+    }
+  }
+}
+
+// pixel p of a (.. x EX_)-pixel region with origin (y0, x0) of an H x W image: its index in the
+// image, or -1 outside the region's NPX pixels or the image
+template <int EX_, int NPX>
+__device__ __forceinline__ int mlp_pixel(int p, int y0, int x0, int H, int W) {
+  const int py = p / EX_, px = p - py * EX_;
+  const int y = y0 + py, x = x0 + px;
+  return (p < NPX && y >= 0 && y < H && x >= 0 && x < W) ? y * W + x : -1;
+}
+
+// fc1 + depthwise 3x3 + act: dw2_fwd_kernel<T, 64, ACT, false> whose LDS image
+// f0 = bf16(x W1^T + b1) is computed (zero outside the image: the conv pads f0, not x) instead of
+// loaded; the inner pixels of f0 also go to memory for the backward and fc1's weight gradient.
+// x (NI, H, W, KC) rows, W1 (G, C, KC), b1 (G, C); C = the hidden width.
+template <typename T, int KC, int ACT>
+__global__ __launch_bounds__(256, 5) void dw2_mlp_fwd_kernel(const T* __restrict__ x, const T* __restrict__ W1,
+                                                             const float* __restrict__ b1, const float* __restrict__ w,
+                                                             const float* __restrict__ b, T* __restrict__ f0,
+                                                             T* __restrict__ out, T* __restrict__ gprime, int ipg,
+                                                             int H, int W, int C, int tiles_x, int tiles_y, int ncb) {
+  constexpr int CB = MLP_CB, PM = MLP_PM, NCQ = CB / 4, NPX = EY * EX, NCH = (NPX + 31) / 32;
+  static_assert(256 / NCQ == TX2, "one tile column per thread");
+  __shared__ __attribute__((aligned(16))) T hs[NPX * PM];
+  const Tile2 t = tile2_of(CB, ipg, tiles_x, tiles_y, ncb);
+  const long pix0 = ((long)t.g * ipg + t.img) * H * W;
+  {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hf = lane >> 5, nh = wv & 1;
+    const int ch0 = t.cb0 + nh * 32;                // this wave's 32 hidden channels
+    typename MF<T>::frag fw[KC / 16];
+    const T* wrow = W1 + ((long)t.g * C + ch0 + r) * KC + 8 * hf;
+#pragma unroll
+    for (int s = 0; s < KC / 16; ++s) fw[s] = MF<T>::load(wrow + 16 * s);
+    // accumulator registers 4 q .. 4 q + 3 of lane half hf are channels ch0 + 8 q + 4 hf + 0 .. 3
+    // (KC = 128: fetched per chunk from L1 / L2 instead, the 16 registers going to the weight fragments)
+    constexpr bool BIAS_REGS = KC == 64;
+    const float* bp = b1 + (long)t.g * C + ch0 + 4 * hf;
+    float4 bv[4];
+    if constexpr (BIAS_REGS) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bv[q] = *reinterpret_cast<const float4*>(bp + 8 * q);
+    }
+    // this wave's chunks wv >> 1, + 2, + 4; a pixel outside the image loads a clamped in-bounds row
+    // unconditionally (see load_vec_if) and stores zeros
+    static_assert(NCH == 6, "three chunks per wave");
+    int pix[3], off[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      pix[j] = mlp_pixel<EX, NPX>(((wv >> 1) + 2 * j) * 32 + r, t.ty0 - 1, t.tx0 - 1, H, W);
+      off[j] = (pix[j] < 0 ? 0 : pix[j]) * KC;
+    }
+    mlp_chunk_stream<T, KC, 3, (KC == 64 ? 8 : 4)>(fw, x + pix0 * KC + 8 * hf, off, [&](int j, const f32x16& acc) {
+      const int p = ((wv >> 1) + 2 * j) * 32 + r;
+      if (p < NPX) {
+        T* d = hs + p * PM + nh * 32 + 4 * hf;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          uint2 v = make_uint2(0, 0);
+          if (pix[j] >= 0) {
+            const float4 bq = BIAS_REGS ? bv[q] : *reinterpret_cast<const float4*>(bp + 8 * q);
+            v = make_uint2(pack2<T>(acc[4 * q] + bq.x, acc[4 * q + 1] + bq.y),
+                           pack2<T>(acc[4 * q + 2] + bq.z, acc[4 * q + 3] + bq.w));
+          }
+          *reinterpret_cast<uint2*>(d + 8 * q) = v;
+        }
+      }
+    });
+  }
+  const int cq = threadIdx.x % NCQ, pl = threadIdx.x / NCQ;
+  const int c0 = t.cb0 + cq * 4;
+  __syncthreads();
+  cmx_f2 wr[2][9], bias[2];
+  load_w36(w + ((long)t.g * C + c0) * 9, wr);
+  if (b) {
+    const float4 b0 = *reinterpret_cast<const float4*>(b + (long)t.g * C + c0);
+    bias[0] = (cmx_f2){b0.x, b0.y}; bias[1] = (cmx_f2){b0.z, b0.w};
+  } else {
+    bias[0] = bias[1] = pk_splat(0.f);
+  }
+  const int xo = t.tx0 + pl;
+  if (xo >= W) return;                              // no barrier after this point
+  dw2_fwd_column<T, ACT, false, PM, true>(hs + pl * PM + cq * 4, wr, bias, out, gprime, f0,
+                                          (pix0 + (long)t.ty0 * W + xo) * C + c0, (long)W * C, H - t.ty0);
 }
 
 // butterfly reduce-scatter of N values over the lanes (xor offsets o): lanes with bit o set
@@ -577,34 +715,38 @@ __device__ __forceinline__ void stage_dz(const T* __restrict__ da, const T* __re
   }
 }
 
+// pixel rounds of the saved-act backward: each thread's h pixels (4 channels, 16 lanes of a pixel
+// = one 128-B row segment at CB = 64) go straight to registers
+template <int CB> constexpr int BWDG_NIT = TYB * TXB / (256 / (CB / 4));
+
 template <typename T, int CB>
-__global__ __launch_bounds__(256, 3) void dw2_bwdg_kernel(const T* __restrict__ da, const T* __restrict__ h,
-                                                       const T* __restrict__ gprime, const float* __restrict__ w,
-                                                       T* __restrict__ dh, float* __restrict__ part, int ipg, int H,
-                                                       int W, int C, int tiles_x, int tiles_y, int ncb, int nsp) {
+__device__ __forceinline__ void bwdg_load_h(const T* __restrict__ h, long ibase, const Tile2& t, int H, int W, int C,
+                                            V4<T> (&hreg)[BWDG_NIT<CB>]) {
   constexpr int NCQ = CB / 4, PPI = 256 / NCQ;
-  constexpr int NE = EYB * EXB, NIN = TYB * TXB;
-  constexpr int LPQ = 64 / NCQ;                     // lanes of one quad in a wave (4 or 8)
-  constexpr int NV = LPQ == 4 ? 10 : 5;             // partials per lane after the in-wave reduce-scatter
-  // only the dz image lives in LDS (41 KB at CB = 64: three blocks per CU); each thread's h
-  // pixels (4 channels, 16 lanes of a pixel = one 128-B row segment) go straight to registers
-  constexpr int NIT = NIN / PPI;
-  __shared__ __attribute__((aligned(16))) T dzs[NE * CB];
-  static_assert(sizeof(dzs) >= 4 * 64 * NV * sizeof(float), "cross-wave reduce buffer");
-  static_assert(NIN % PPI == 0, "pixel rounds");
-  const Tile2 t = tile2_of<TYB, TXB>(CB, ipg, tiles_x, tiles_y, ncb);
-  const long ibase = ((long)t.g * ipg + t.img) * H * W * C + t.cb0;
-  stage_dz<T, CB>(da + ibase, gprime + ibase, dzs, t.ty0, t.tx0, H, W, C);
+  static_assert(TYB * TXB % PPI == 0, "pixel rounds");
   const int cq = threadIdx.x % NCQ, pl = threadIdx.x / NCQ;
-  const int c0 = t.cb0 + cq * 4;
-  V4<T> hreg[NIT];
 #pragma unroll
-  for (int k = 0; k < NIT; ++k) {
+  for (int k = 0; k < BWDG_NIT<CB>; ++k) {
     const int it = pl + k * PPI;
     const int y = t.ty0 + it / TXB, x = t.tx0 + it % TXB;
     hreg[k].a = {};
     if (y < H && x < W) hreg[k] = v4_load<T>(h + ibase + ((long)y * W + x) * C + cq * 4);
   }
+}
+
+// the saved-act backward from the barrier that completes the dz image (PITCH elements per pixel,
+// NBYTES of LDS) to the block's partial slab
+template <typename T, int CB, int PITCH, int NBYTES>
+__device__ __forceinline__ void bwdg_from_dz(T* dzs, const V4<T> (&hreg)[BWDG_NIT<CB>], const float* __restrict__ w,
+                                             T* __restrict__ dh, float* __restrict__ part, const Tile2& t, long ibase,
+                                             int H, int W, int C, int nsp) {
+  constexpr int NCQ = CB / 4, PPI = 256 / NCQ;
+  constexpr int LPQ = 64 / NCQ;                     // lanes of one quad in a wave (4 or 8)
+  constexpr int NV = LPQ == 4 ? 10 : 5;             // partials per lane after the in-wave reduce-scatter
+  constexpr int NIT = BWDG_NIT<CB>;
+  static_assert(NBYTES >= 4 * 64 * NV * (int)sizeof(float), "cross-wave reduce buffer");
+  const int cq = threadIdx.x % NCQ, pl = threadIdx.x / NCQ;
+  const int c0 = t.cb0 + cq * 4;
   __syncthreads();
   cmx_f2 wr[2][9];
   load_w36(w + ((long)t.g * C + c0) * 9, wr);
@@ -622,12 +764,12 @@ __global__ __launch_bounds__(256, 3) void dw2_bwdg_kernel(const T* __restrict__ 
     const int x = t.tx0 + pl;
     const int nr = H - t.ty0;
     if (x < W) {
-      const T* dzp = dzc + pl * CB;
+      const T* dzp = dzc + pl * PITCH;
       cmx_f2 win[3][3][2];                          // [dz row % 3][column c .. c+2][pair]
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        v4_unpack<T>(v4_load<T>(dzp + j * CB), win[0][j]);
-        v4_unpack<T>(v4_load<T>(dzp + (EXB + j) * CB), win[1][j]);
+        v4_unpack<T>(v4_load<T>(dzp + j * PITCH), win[0][j]);
+        v4_unpack<T>(v4_load<T>(dzp + (EXB + j) * PITCH), win[1][j]);
       }
       long o = ibase + ((long)t.ty0 * W + x) * C + cq * 4;
       const long ostep = (long)W * C;
@@ -635,7 +777,7 @@ __global__ __launch_bounds__(256, 3) void dw2_bwdg_kernel(const T* __restrict__ 
       for (int k = 0; k < NIT; ++k) {
         if (k < nr) {
 #pragma unroll
-          for (int j = 0; j < 3; ++j) v4_unpack<T>(v4_load<T>(dzp + ((k + 2) * EXB + j) * CB), win[(k + 2) % 3][j]);
+          for (int j = 0; j < 3; ++j) v4_unpack<T>(v4_load<T>(dzp + ((k + 2) * EXB + j) * PITCH), win[(k + 2) % 3][j]);
           cmx_f2 hv[2];
           v4_unpack<T>(hreg[k], hv);
           cmx_f2 g[2] = {pk_splat(0.f), pk_splat(0.f)};
@@ -674,7 +816,7 @@ __global__ __launch_bounds__(256, 3) void dw2_bwdg_kernel(const T* __restrict__ 
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           cmx_f2 dv[2];
-          v4_unpack<T>(v4_load<T>(dzc + ((r + 2 - i) * EXB + c + 2 - j) * CB), dv);
+          v4_unpack<T>(v4_load<T>(dzc + ((r + 2 - i) * EXB + c + 2 - j) * PITCH), dv);
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
             g[u] = pk_fma(wr[u][i * 3 + j], dv[u], g[u]);
@@ -725,6 +867,79 @@ __global__ __launch_bounds__(256, 3) void dw2_bwdg_kernel(const T* __restrict__ 
     for (int bit = 0; bit < (NV == 5 ? 3 : 2); ++bit) sgi = sgi * 2 + ((sg >> bit) & 1);
     o[q * 40 + sgi * NV + k] = v;
   }
+}
+
+template <typename T, int CB>
+__global__ __launch_bounds__(256, 3) void dw2_bwdg_kernel(const T* __restrict__ da, const T* __restrict__ h,
+                                                       const T* __restrict__ gprime, const float* __restrict__ w,
+                                                       T* __restrict__ dh, float* __restrict__ part, int ipg, int H,
+                                                       int W, int C, int tiles_x, int tiles_y, int ncb, int nsp) {
+  // only the dz image lives in LDS (41 KB at CB = 64: three blocks per CU)
+  __shared__ __attribute__((aligned(16))) T dzs[EYB * EXB * CB];
+  const Tile2 t = tile2_of<TYB, TXB>(CB, ipg, tiles_x, tiles_y, ncb);
+  const long ibase = ((long)t.g * ipg + t.img) * H * W * C + t.cb0;
+  stage_dz<T, CB>(da + ibase, gprime + ibase, dzs, t.ty0, t.tx0, H, W, C);
+  V4<T> hreg[BWDG_NIT<CB>];
+  bwdg_load_h<T, CB>(h, ibase, t, H, W, C, hreg);
+  bwdg_from_dz<T, CB, CB, (int)sizeof(dzs)>(dzs, hreg, w, dh, part, t, ibase, H, W, C, nsp);
+}
+
+// fc2's input gradient + depthwise backward from saved act'(z): dw2_bwdg_kernel<T, 64> whose
+// da = bf16(dz2 W2) is computed on the tile + halo instead of loaded (it never reaches memory).
+// act'(z) is staged into the LDS image first (coalesced 16-B loads); each lane then multiplies
+// its own da values into it in place, rounding as stage_dz does.  dz2 (NI, H, W, KC) rows = fc2's
+// (DropPath-scaled) output gradient, W2 (G, KC, C): the product runs over W2's rows, so a lane's
+// 8 consecutive k are a strided gather (once per block, from L2).
+template <typename T, int KC>
+__global__ __launch_bounds__(256, 3) void dw2_mlp_bwdg_kernel(const T* __restrict__ dz2, const T* __restrict__ W2,
+                                                              const T* __restrict__ h, const T* __restrict__ gprime,
+                                                              const float* __restrict__ w, T* __restrict__ dh,
+                                                              float* __restrict__ part, int ipg, int H, int W, int C,
+                                                              int tiles_x, int tiles_y, int ncb, int nsp) {
+  constexpr int CB = MLP_CB, PM = MLP_PM, NE = EYB * EXB, NCH = (NE + 31) / 32;
+  __shared__ __attribute__((aligned(16))) T dzs[NE * PM];
+  const Tile2 t = tile2_of<TYB, TXB>(CB, ipg, tiles_x, tiles_y, ncb);
+  const long pix0 = ((long)t.g * ipg + t.img) * H * W;
+  const long ibase = pix0 * C + t.cb0;
+  stage_region_pm<T, CB, EYB, EXB, PM>(gprime + ibase, dzs, t.ty0 - 1, t.tx0 - 1, H, W, C);
+  V4<T> hreg[BWDG_NIT<CB>];
+  bwdg_load_h<T, CB>(h, ibase, t, H, W, C, hreg);
+  {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hf = lane >> 5, nh = wv & 1;
+    typename MF<T>::frag fw[KC / 16];
+    const T* wcol = W2 + (long)t.g * KC * C + t.cb0 + nh * 32 + r;   // hidden channel of this lane's row
+#pragma unroll
+    for (int s = 0; s < KC / 16; ++s) {
+      T e[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) e[k] = wcol[(long)(16 * s + 8 * hf + k) * C];
+      fw[s] = frag_bits<T>(pack_raw<T>(e));
+    }
+    // this wave's chunks wv >> 1, + 2, ..: six of them (the last is empty for waves 2, 3: NCH = 11);
+    // a pixel outside the image (or the region) loads a clamped in-bounds row and keeps the staged zeros
+    constexpr int NCW = (NCH + 1) / 2;
+    int pix[NCW], off[NCW];
+#pragma unroll
+    for (int j = 0; j < NCW; ++j) {
+      pix[j] = mlp_pixel<EXB, NE>(((wv >> 1) + 2 * j) * 32 + r, t.ty0 - 1, t.tx0 - 1, H, W);
+      off[j] = (pix[j] < 0 ? 0 : pix[j]) * KC;
+    }
+    mlp_chunk_stream<T, KC, NCW, 8>(fw, dz2 + pix0 * KC + 8 * hf, off, [&](int j, const f32x16& acc) {
+      if (j == 0) __syncthreads();                  // the act'(z) image is complete (every wave passes here once)
+      if (pix[j] >= 0) {
+        T* d = dzs + (((wv >> 1) + 2 * j) * 32 + r) * PM + nh * 32 + 4 * hf;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint2 g = *reinterpret_cast<const uint2*>(d + 8 * q);
+          // da as the GEMM would have stored it, then dz = da * act'(z) as stage_dz forms it
+          const cmx_f2 d0 = unpack2<T>(pack2<T>(acc[4 * q], acc[4 * q + 1])) * unpack2<T>(g.x);
+          const cmx_f2 d1 = unpack2<T>(pack2<T>(acc[4 * q + 2], acc[4 * q + 3])) * unpack2<T>(g.y);
+          *reinterpret_cast<uint2*>(d + 8 * q) = make_uint2(pack2<T>(d0.x, d0.y), pack2<T>(d1.x, d1.y));
+        }
+      }
+    });
+  }
+  bwdg_from_dz<T, CB, PM, (int)sizeof(dzs)>(dzs, hreg, w, dh, part, t, ibase, H, W, C, nsp);
 }
 
 
@@ -864,6 +1079,25 @@ int bwd_slots(int CQ, int nstrips) {
 // (fp32 parity mode: 32-channel blocks, so the backward's three tiles fit twice per CU)
 static int tile_cb(int C, int dtype) { return (C % 64 == 0 && (dtype == 1 || dtype == 2)) ? 64 : C % 32 == 0 ? 32 : 0; }
 
+// the Mix-FFN fusion (dw2_mlp_*_kernel): 16-bit storage, K = C in registers, 64-channel blocks
+static bool mlp_fusable(int C, int hidden, int dtype) {
+  return (dtype == 1 || dtype == 2) && (C == 64 || C == 128) && hidden > 0 && hidden % MLP_CB == 0;
+}
+
+// after a backward's launch: the (G, P, C * 10) partials stay in the workspace for a deferred
+// reduce (dw = db = NULL), or are folded into dw (G, C, 9) / db (G, C) now
+static int fold_partials(float* workspace, float* dw, float* db, int G, int P, int C, int accumulate, const char* what,
+                         hipStream_t s) {
+  if (!dw && !db) return cmx_check_launch(what);
+  float* tmp = workspace + (size_t)G * P * C * 10;
+  int st = cmx_reduce_partials(workspace, tmp, G, P, C * 10, 0, 1.f, s);
+  if (st) return st;
+  const long tot = (long)G * C * 10;
+  hipLaunchKernelGGL(dw_scatter_kernel, dim3(cdiv(tot, 256) < 4096 ? cdiv(tot, 256) : 4096), dim3(256), 0, s, tmp, dw,
+                     db, G, C, accumulate);
+  return cmx_check_launch(what);
+}
+
 extern "C" {
 
 int cmx_dwconv3x3_fwd(const void* h, const float* w, const float* b, void* out, int NI, int imgs_per_group, int H,
@@ -924,14 +1158,63 @@ int cmx_dwconv3x3_bwd_saved(const void* da, const void* h, const void* gprime, c
                          (const T*)gprime, w, (T*)dh, workspace, imgs_per_group, H, W, C, tx, ty, ncb, P);
     }
   });
-  if (!dw && !db) return cmx_check_launch("dwconv_bwd_saved");
-  float* tmp = workspace + (size_t)G * P * C * 10;
-  int st = cmx_reduce_partials(workspace, tmp, G, P, C * 10, 0, 1.f, s);
-  if (st) return st;
-  const long tot = (long)G * C * 10;
-  hipLaunchKernelGGL(dw_scatter_kernel, dim3(cdiv(tot, 256) < 4096 ? cdiv(tot, 256) : 4096), dim3(256), 0, s, tmp, dw,
-                     db, G, C, accumulate);
-  return cmx_check_launch("dwconv_bwd_saved");
+  return fold_partials(workspace, dw, db, G, P, C, accumulate, "dwconv_bwd_saved", s);
+}
+
+int cmx_mlp_fc1_dwconv_fwd(const void* x, const void* W1, const float* b1, const float* w, const float* b, void* f0,
+                           void* out, void* gprime, int NI, int imgs_per_group, int H, int W, int C, int hidden,
+                           int act, int dtype, hipStream_t s) {
+  CMX_REQUIRE(mlp_fusable(C, hidden, dtype) && act == ACT_GELU, CMX_ERR_SHAPE,
+              "mlp_fc1_dwconv_fwd: C=%d hidden=%d dtype=%d act=%d (16-bit, C 64 / 128, hidden %% 64 == 0, GELU)", C,
+              hidden, dtype, act);
+  CMX_REQUIRE(NI > 0 && imgs_per_group > 0 && NI % imgs_per_group == 0 && H > 0 && W > 0, CMX_ERR_SHAPE,
+              "mlp_fc1_dwconv_fwd: NI=%d imgs_per_group=%d H=%d W=%d", NI, imgs_per_group, H, W);
+  CMX_REQUIRE(x && W1 && b1 && w && f0 && out && gprime, CMX_ERR_ARG, "mlp_fc1_dwconv_fwd: null operand");
+  CMX_REQUIRE((long)NI * H * W * hidden < (1L << 31), CMX_ERR_SHAPE, "mlp_fc1_dwconv_fwd: tensor too large");
+  const int G = NI / imgs_per_group;
+  const int tx = cdiv(W, TX2), ty = cdiv(H, TY2), ncb = hidden / MLP_CB;
+  const dim3 grid((unsigned)imgs_per_group * ty * tx * ncb, G);
+  CMX_DISPATCH(dtype, T, {
+    if constexpr (sizeof(T) == 2) {
+      if (C == 64) {
+        hipLaunchKernelGGL((dw2_mlp_fwd_kernel<T, 64, ACT_GELU>), grid, dim3(256), 0, s, (const T*)x, (const T*)W1, b1,
+                           w, b, (T*)f0, (T*)out, (T*)gprime, imgs_per_group, H, W, hidden, tx, ty, ncb);
+      } else {
+        hipLaunchKernelGGL((dw2_mlp_fwd_kernel<T, 128, ACT_GELU>), grid, dim3(256), 0, s, (const T*)x, (const T*)W1,
+                           b1, w, b, (T*)f0, (T*)out, (T*)gprime, imgs_per_group, H, W, hidden, tx, ty, ncb);
+      }
+    }
+  });
+  return cmx_check_launch("mlp_fc1_dwconv_fwd");
+}
+
+int cmx_mlp_fc2_dwconv_bwd(const void* dz, const void* W2, const void* h, const void* gprime, const float* w, void* dh,
+                           float* dw, float* db, float* workspace, int NI, int imgs_per_group, int H, int W, int C,
+                           int hidden, int accumulate, int dtype, hipStream_t s) {
+  CMX_REQUIRE(mlp_fusable(C, hidden, dtype), CMX_ERR_SHAPE,
+              "mlp_fc2_dwconv_bwd: C=%d hidden=%d dtype=%d (16-bit, C 64 / 128, hidden %% 64 == 0)", C, hidden, dtype);
+  CMX_REQUIRE(NI > 0 && imgs_per_group > 0 && NI % imgs_per_group == 0 && H > 0 && W > 0, CMX_ERR_SHAPE,
+              "mlp_fc2_dwconv_bwd: NI=%d imgs_per_group=%d H=%d W=%d", NI, imgs_per_group, H, W);
+  CMX_REQUIRE(dz && W2 && h && gprime && w && workspace, CMX_ERR_ARG, "mlp_fc2_dwconv_bwd: null operand");
+  CMX_REQUIRE((long)NI * H * W * hidden < (1L << 31), CMX_ERR_SHAPE, "mlp_fc2_dwconv_bwd: tensor too large");
+  const int G = NI / imgs_per_group;
+  const int tx = cdiv(W, TXB), ty = cdiv(H, TYB), ncb = hidden / MLP_CB;
+  const int P = imgs_per_group * ty * tx;
+  const dim3 grid((unsigned)P * ncb, G);
+  CMX_DISPATCH(dtype, T, {
+    if constexpr (sizeof(T) == 2) {
+      if (C == 64) {
+        hipLaunchKernelGGL((dw2_mlp_bwdg_kernel<T, 64>), grid, dim3(256), 0, s, (const T*)dz, (const T*)W2,
+                           (const T*)h, (const T*)gprime, w, (T*)dh, workspace, imgs_per_group, H, W, hidden, tx, ty,
+                           ncb, P);
+      } else {
+        hipLaunchKernelGGL((dw2_mlp_bwdg_kernel<T, 128>), grid, dim3(256), 0, s, (const T*)dz, (const T*)W2,
+                           (const T*)h, (const T*)gprime, w, (T*)dh, workspace, imgs_per_group, H, W, hidden, tx, ty,
+                           ncb, P);
+      }
+    }
+  });
+  return fold_partials(workspace, dw, db, G, P, hidden, accumulate, "mlp_fc2_dwconv_bwd", s);
 }
 
 // partial-slab count (tiles per group) of cmx_dwconv3x3_bwd_saved: its dW / db partials occupy
@@ -999,14 +1282,7 @@ int cmx_dwconv3x3_bwd(const void* da, const void* h, const float* w, const float
       }
     });
   }
-  if (!dw && !db) return cmx_check_launch("dwconv_bwd");   // partials (G, P, C*10) left for a deferred reduce
-  float* tmp = workspace + (size_t)G * P * C * 10;
-  int st = cmx_reduce_partials(workspace, tmp, G, P, C * 10, 0, 1.f, s);
-  if (st) return st;
-  const long tot = (long)G * C * 10;
-  hipLaunchKernelGGL(dw_scatter_kernel, dim3(cdiv(tot, 256) < 4096 ? cdiv(tot, 256) : 4096), dim3(256), 0, s, tmp, dw,
-                     db, G, C, accumulate);
-  return cmx_check_launch("dwconv_bwd");
+  return fold_partials(workspace, dw, db, G, P, C, accumulate, "dwconv_bwd", s);
 }
 
 }  // extern "C"

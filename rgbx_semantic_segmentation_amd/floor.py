@@ -35,9 +35,10 @@ def step_work(backbone="mit_b2", H=480, W=640, B=2, K=40, E=512, n_params=None):
         fam[f][0] += flops
         fam[f][1] += byts
 
-    def gemm(M, N, Kd, G=1, res=False, wgrad=True, dgrad=True, bias_grad=True):
+    def gemm(M, N, Kd, G=1, res=False, wgrad=True, dgrad=True, bias_grad=True, fwd=True):
         # forward y = x W^T (+ residual), dgrad dx = dy W, wgrad dW = dy^T x (fp32 out)
-        add("gemm", 2 * G * M * N * Kd, G * A * (M * Kd + N * Kd + M * N + (M * N if res else 0)))
+        if fwd:
+            add("gemm", 2 * G * M * N * Kd, G * A * (M * Kd + N * Kd + M * N + (M * N if res else 0)))
         if dgrad:
             add("gemm", 2 * G * M * N * Kd, G * A * (M * N + N * Kd + M * Kd))
         if wgrad:
@@ -47,7 +48,14 @@ def step_work(backbone="mit_b2", H=480, W=640, B=2, K=40, E=512, n_params=None):
         add("layernorm", 0, G * A * rows * C * 2 + G * F32 * 2 * rows)                 # fwd: x -> y, mean / rstd
         add("layernorm", 0, G * A * rows * C * (3 + (1 if two else 0) + (1 if tap else 0)) + G * F32 * 2 * rows)
 
-    def dw(M_pix, C, G=1):
+    def dw(M_pix, C, G=1, fc=0):
+        # fc = K of the Linears computed inside the kernels (MlpF, Mix-FFN of stages 1-2; 0: none): the forward
+        # forms h = x W1^T from x, W1 and writes it; the backward forms da = dz W2 from dz, W2 and never stores it
+        if fc:
+            lin = 2 * G * M_pix * C * fc, G * A * (M_pix * fc + C * fc)
+            add("dwconv", 2 * 9 * G * M_pix * C * 3 + lin[0], G * A * M_pix * C * 3 + lin[1])   # fwd: x, W1 -> h, out, act'
+            add("dwconv", lin[0], G * A * M_pix * C * 3 + lin[1])                    # bwd: dz, W2, act', h -> dh
+            return
         add("dwconv", 2 * 9 * G * M_pix * C * 3, G * A * M_pix * C * 3)              # fwd: h -> out, act'
         add("dwconv", 0, G * A * M_pix * C * 4)                                      # bwd: da, act', h -> dh
 
@@ -93,9 +101,10 @@ def step_work(backbone="mit_b2", H=480, W=640, B=2, K=40, E=512, n_params=None):
             add("sra", 2.5 * fwd_f, G * A * (3 * M * C + Mk * 2 * C + M * C + Mk * 2 * C) + G * F32 * B * NUM_HEADS[s] * N * 2)
             gemm(M, C, C, G, res=True)                                                # proj + residual
             ln(M, C, G, tap=True)                                                     # norm2
-            gemm(M, 4 * C, C, G)                                                      # fc1
-            dw(M, 4 * C, G)
-            gemm(M, C, 4 * C, G, res=True)                                            # fc2 + residual
+            fused = C in (64, 128)              # MlpF: fc1's forward and fc2's dgrad run in the depthwise kernels
+            gemm(M, 4 * C, C, G, fwd=not fused)                                       # fc1
+            dw(M, 4 * C, G, fc=C if fused else 0)
+            gemm(M, C, 4 * C, G, res=True, dgrad=not fused)                           # fc2 + residual
         ln(M, C, G, tap=True)                                                         # stage norm
         # CM-FRM: pool, channel MLP (fp32 weights), spatial 2C -> C GEMM, combine, backward
         add("frm", 0, G * A * M * C)                                                  # pool

@@ -655,6 +655,129 @@ def dwconv(store, conv, h, NI, ipg, H, W, act):
     return DWConvF.apply(h, w, b, wg, bg, NI, ipg, H, W, act, conv.weight)
 
 
+# CMX_MLP_FUSE (A/B switch, stages 1-2: C 64 / 128, 16-bit): bit 0 = fc1 runs inside the depthwise
+# forward (cmx_mlp_fc1_dwconv_fwd), bit 1 = fc2's input gradient runs inside the depthwise backward
+# (cmx_mlp_fc2_dwconv_bwd, the gradient never stored); 0 = the separate GLinear / DWConvF launches.
+# Either way the results are bit-identical.
+MLP_FUSE = int(os.environ.get("CMX_MLP_FUSE", "3"))
+
+
+class MlpF(Function):
+    """Mix-FFN as one node: y = res + rscale * (fc2(gelu(dwconv3x3(fc1(x))))), i.e. GLinear ->
+    DWConvF -> GLinear with the middle hand-overs inside (dual_segformer.py:67-74, 168-169).  fc1's
+    backward (dgrad_tap / deferred wgrad) and fc2's forward (residual, DropPath scale, LN tail) and
+    deferred wgrad are GLinear's; ``fuse`` = the MLP_FUSE bits in force."""
+
+    @staticmethod
+    def forward(ctx, x, res, W1, Wg1, b1, bg1, dw_w, dw_b, dw_wg, dw_bg, W2, Wg2, b2, bg2, a1, a2, a3, geom, rscale,
+                rps, tap, ln, dgrad_tap, fuse):
+        NI, ipg, H, Wd = geom
+        G, M, C = x.shape
+        hidden = W1.shape[1]
+        dt = K.dtype_code(x)
+        f0 = torch.empty(G, M, hidden, dtype=x.dtype, device=x.device)
+        f = torch.empty_like(f0)
+        gprime = torch.empty_like(f0)
+        if fuse & 1:
+            K.call("cmx_mlp_fc1_dwconv_fwd", x, W1, b1, dw_w, dw_b, f0, f, gprime, NI, ipg, H, Wd, C, hidden,
+                   K.ACT["gelu"], dt)
+        else:
+            _fwd_gemm(x, W1, b1, f0)
+            K.call("cmx_dwconv3x3_fwd_save", f0, dw_w, dw_b, f, gprime, NI, ipg, H, Wd, hidden, K.ACT["gelu"], dt)
+        y = torch.empty(G, M, W2.shape[1], dtype=x.dtype, device=x.device)
+        pre = None
+        if ln is not None:                   # the consumer LayerNorm in fc2's launch (see GLinear.forward)
+            gamma, beta, eps, sink = ln
+            pre = K.gemm_ln(f, W2, y, gamma, beta, eps, bias=b2, residual=res, rscale=rscale, rows_per_sample=rps)
+            sink.pre = pre
+        if pre is None:
+            _fwd_gemm(f, W2, b2, y, res=res, rscale=rscale, rps=rps)
+        ctx.save_for_backward(x, W1, f0, gprime, dw_w, f, W2)
+        ctx.meta = (Wg1, bg1, dw_wg, dw_bg, Wg2, bg2, geom, res is not None, rscale, rps, tap, dgrad_tap, fuse)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W1, f0, gprime, dw_w, f, W2 = ctx.saved_tensors
+        Wg1, bg1, dw_wg, dw_bg, Wg2, bg2, geom, has_res, rscale, rps, tap, dgrad_tap, fuse = ctx.meta
+        NI, ipg, H, Wd = geom
+        dy = _c(dy)
+        G, M, C = dy.shape
+        hidden = f0.shape[-1]
+        dt = K.dtype_code(x)
+        dres = dy if has_res else None
+        dz = dy
+        if rscale is not None:               # the DropPath-scaled gradient (see GLinear.backward)
+            dz = tap.take(dy) if tap is not None else None
+            if dz is None:
+                dz = K.scale_samples(dy, rscale, rps * C)
+        dz = _c(dz)
+        nbytes = K.query("cmx_dwconv3x3_bwd_workspace", NI, ipg, H, Wd, hidden)
+        defer = deferred.ENABLED
+        dw, db = (None, None) if defer else (dw_wg, dw_bg)
+        dh = torch.empty_like(f0)
+        if fuse & 2:
+            _wgrad_into(dz, f, Wg2, bg2)
+            ws = K._ws(nbytes, x.device)
+            K.call("cmx_mlp_fc2_dwconv_bwd", dz, W2, f0, gprime, dw_w, dh, dw, db, ws, NI, ipg, H, Wd, C, hidden, 0, dt)
+        else:
+            da = _dgrad(dz, W2, torch.empty_like(f))
+            _wgrad_into(dz, f, Wg2, bg2)
+            ws = K._ws(nbytes, x.device)
+            K.call("cmx_dwconv3x3_bwd_saved", da, f0, gprime, dw_w, dh, dw, db, ws, NI, ipg, H, Wd, hidden, 0, dt)
+        if defer:
+            P = K.query("cmx_dwconv3x3_bwd_saved_tiles", ipg, H, Wd)
+            deferred.reduce(ws, dw_wg, dw_bg, G, P, P * hidden * 10, hidden * 10, hidden, 10, 9, dw_wg.stride(0), 9,
+                            dw_bg.stride(0), 1)
+        dx = None
+        if dgrad_tap is not None and ctx.needs_input_grad[0]:
+            dgrad_tap.put((dh, W1))          # the producing norm's backward runs this dgrad (see GLinear.backward)
+        elif ctx.needs_input_grad[0]:
+            dx = _dgrad(dh, W1, torch.empty_like(x))
+        _wgrad_into(dh, x, Wg1, bg1)
+        return (dx, dres) + (None,) * 22
+
+
+def mlp_fusable(x, W1, b1, W2) -> bool:
+    """Block's Mix-FFN can run as MlpF: MLP_FUSE set, 16-bit, C 64 / 128 (stages 1-2), hidden in
+    64-channel blocks, operands as the entry points read them (contiguous)."""
+    C, hidden = x.shape[-1], W1.shape[1]
+    return (MLP_FUSE & 3 != 0 and x.dtype in (torch.bfloat16, torch.float16) and C in (64, 128) and hidden % 64 == 0
+            and b1 is not None and x.is_contiguous() and W1.is_contiguous() and b1.is_contiguous()
+            and W2.is_contiguous() and tuple(W2.shape[1:]) == (C, hidden))
+
+
+def mlp(store, m, x, NI, ipg, H, W, res=None, rscale=None, rps=1, tap=None, ln_tail=None, dgrad_tap=None):
+    """Block's Mix-FFN (fc1 -> DWConv + GELU -> fc2 with the residual) on x; the arguments are those
+    of the glinear / dwconv calls it stands for.  Stages 1-2 run as MlpF, the rest as those calls."""
+    G = x.shape[0]
+
+    def lin(layer):
+        W, Wg = store.w(layer.weight), store.g(layer.weight)
+        return (W.view(G, W.shape[1], -1), Wg.view(G, Wg.shape[1], -1), store.w(layer.bias, compute=False).view(G, -1),
+                store.g(layer.bias).view(G, -1))
+
+    W1, Wg1, b1, bg1 = lin(m.fc1)
+    W2, Wg2, b2, bg2 = lin(m.fc2)
+    if not mlp_fusable(x, W1, b1, W2):
+        f = glinear(store, m.fc1.weight, m.fc1.bias, x, dgrad_tap=dgrad_tap)
+        f = dwconv(store, m.dwconv.dwconv, f, NI, ipg, H, W, "gelu")
+        return glinear(store, m.fc2.weight, m.fc2.bias, f, res=res, rscale=rscale, rps=rps, tap=tap, ln_tail=ln_tail)
+    conv = m.dwconv.dwconv
+    dw_w = store.w(conv.weight, compute=False).view(G, -1, 9)
+    dw_b = store.w(conv.bias, compute=False).view(G, -1)
+    dw_wg = store.g(conv.weight).view(G, -1, 9)
+    dw_bg = store.g(conv.bias).view(G, -1)
+    ln = None
+    N = W2.shape[1]
+    if ln_tail is not None and LN_ROW and N <= 128 and N % 8 == 0:
+        nm = ln_tail.mod
+        ln = (store.w(nm.weight, compute=False).view(G, -1), store.w(nm.bias, compute=False).view(G, -1), nm.eps,
+              ln_tail)
+    return MlpF.apply(x, res, W1, Wg1, b1, bg1, dw_w, dw_b, dw_wg, dw_bg, W2, Wg2, b2, bg2, m.fc1.weight,
+                      conv.weight, m.fc2.weight, (NI, ipg, H, W), rscale, rps, tap, ln, dgrad_tap, MLP_FUSE)
+
+
 class DgradTap:
     """Side channel from a GLinear's backward to the producer of its input: (dz, W) handed over
     instead of the GLinear launching dx = dz W itself (the producing norm's backward runs that

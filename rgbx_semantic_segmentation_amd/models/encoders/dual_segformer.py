@@ -254,12 +254,12 @@ class RGBXTransformer(nn.Module):                 # dual_segformer.py:228-446
         # norm2's backward rides on fc1's dgrad launch (C <= 128): fc1 hands (dz, W1) over
         ltap = F.DgradTap() if F.ln_bwd_fusable(x) else None
         h, _, xr = F.layernorm_res(store, blk.norm2, x, G, scale=s_attn, rps=N, tap=tap_a, tail=t2, dtap=ltap)
-        f = F.glinear(store, blk.mlp.fc1.weight, blk.mlp.fc1.bias, h, dgrad_tap=ltap)
-        f = F.dwconv(store, blk.mlp.dwconv.dwconv, f, G * B, B, H, W, "gelu")
         tap_m = F.GradTap() if s_mlp is not None else None
         tn = F.LNTail(next_norm) if next_norm is not None else None
-        x = F.glinear(store, blk.mlp.fc2.weight, blk.mlp.fc2.bias, f, res=xr, rscale=s_mlp, rps=N, tap=tap_m,
-                      ln_tail=tn)
+        # fc1 -> DWConv + GELU -> fc2 (+ residual); at C 64 / 128 fc1 and fc2's input gradient run inside
+        # the depthwise kernels (F.MlpF)
+        x = F.mlp(store, blk.mlp, h, G * B, B, H, W, res=xr, rscale=s_mlp, rps=N, tap=tap_m, ln_tail=tn,
+                  dgrad_tap=ltap)
         return x, (s_mlp, tap_m), tn
 
     def run(self, store, images, B, H, W, training, dp_scales: Optional[torch.Tensor], bn_group=None, aspp_mask=None):

@@ -97,7 +97,7 @@ FAMILY_RE = (
     ("wgrad", r"gemm_grouped_kernel|reduce_grouped_kernel"),
     ("gemm", r"gemm_bf16_kernel|gemm_stream|gemm_multi|gemm_generic|splitk_reduce"),
     ("sra", r"sra_"),
-    ("dwconv", r"dw2_|dw_"),
+    ("dwconv", r"dw2_mlp_|dw2_|dw_"),       # dw2_mlp_*: the Mix-FFN kernels that also run fc1 / fc2's dgrad
     ("layernorm", r"ln_fwd|ln_bwd|rowln"),
     ("adamw", r"adamw"),
     ("batchnorm", r"bn_"),

@@ -55,6 +55,31 @@ def main():
         nb = h.numel() * 2
         print(f"H{H} W{W} C{C}: fwd_save {tf:7.1f} us {3 * nb / tf / 1e3:6.0f} GB/s   "
               f"bwd_saved(+reduce) {tb:7.1f} us {4 * nb / tb / 1e3:6.0f} GB/s  (tensor {nb / 1e6:.1f} MB)")
+        if C // 4 in (64, 128):
+            mlp_fused(G, B, H, W, C // 4, C, h, w, b, out, gp, dh, dw, db, ws, tf, tb)
+
+
+def mlp_fused(G, B, H, W, C, hidden, f0, w, b, out, gp, dh, dw, db, ws, tf, tb):
+    """Stages 1-2: fc1 + the forward and fc2's dgrad + the backward as the two launches of today (GEMM, then the
+    depthwise kernel timed above) against the one launch of cmx_mlp_fc1_dwconv_fwd / cmx_mlp_fc2_dwconv_bwd."""
+    NI, M = G * B, B * H * W
+    x = torch.randn(G, M, C, device="cuda").bfloat16()
+    dz = torch.randn(G, M, C, device="cuda").bfloat16()
+    W1 = (torch.randn(G, hidden, C, device="cuda") * C ** -0.5).bfloat16()
+    W2 = (torch.randn(G, C, hidden, device="cuda") * hidden ** -0.5).bfloat16()
+    b1 = torch.randn(G, hidden, device="cuda") * 0.1
+    f0v, da = f0.view(G, M, hidden), torch.empty(G, M, hidden, device="cuda", dtype=torch.bfloat16)
+    ACT = Kn.ACT["gelu"]
+    t_fc1 = timeit(lambda: Kn.gemm(x, W1, f0v, bias=b1))
+    t_dg = timeit(lambda: Kn.gemm(dz, W2.transpose(1, 2), da))
+    t_ff = timeit(lambda: Kn.call("cmx_mlp_fc1_dwconv_fwd", x, W1, b1, w, b, f0, out, gp, NI, B, H, W, C, hidden, ACT, 1))
+    t_fb = timeit(lambda: Kn.call("cmx_mlp_fc2_dwconv_bwd", dz, W2, f0, gp, w, dh, dw, db, ws, NI, B, H, W, C, hidden,
+                                  0, 1))
+    nb = f0.numel() * 2
+    print(f"   fc1 GEMM {t_fc1:6.1f} us + fwd_save = {t_fc1 + tf:6.1f} us | fused forward {t_ff:6.1f} us "
+          f"{3 * nb / t_ff / 1e3:6.0f} GB/s")
+    print(f"   fc2 dgrad GEMM {t_dg:6.1f} us + bwd_saved(+reduce) = {t_dg + tb:6.1f} us | fused backward(+reduce) "
+          f"{t_fb:6.1f} us {3 * nb / t_fb / 1e3:6.0f} GB/s")
 
 
 if __name__ == "__main__":

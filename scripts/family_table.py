@@ -41,7 +41,7 @@ def work():
     from rgbx_semantic_segmentation_amd.floor import step_work
     w = step_work(backbone="mit_b2", H=H, W=W, B=B, K=K, E=E, n_params=66.58e6)
     names = {"gemm": "GEMM fwd+dgrad (tile / streaming / k-group / multi / split-K)", "wgrad": "grouped wgrad GEMM + grouped reduce",
-             "sra": "SRA attention (fwd, dQ, dK/dV, reduce)", "dwconv": "DWConv 3x3 + GELU (fwd_save, bwd_saved)",
+             "sra": "SRA attention (fwd, dQ, dK/dV, reduce)", "dwconv": "DWConv 3x3 + GELU (fwd_save, bwd_saved, fc1 / fc2-dgrad fused)",
              "layernorm": "LayerNorm (fwd, bwd)", "adamw": "AdamW", "batchnorm": "BatchNorm (stats, fold, apply, bwd)",
              "frm": "FRM (pool, channel MLP, combine)", "ffm": "FFM context / cross attention",
              "ce": "upsample + CE", "bilinear": "bilinear (decoder fuse adjoint)", "im2col": "im2col / col2im",
@@ -56,7 +56,7 @@ FAMILIES = [
     ("Mix-FFN bands", r"mixffn_"),
     ("GEMM fwd+dgrad (tile / streaming / k-group / multi / split-K)", r"gemm_bf16_kernel|gemm_stream|gemm_multi|gemm_generic|splitk_reduce"),
     ("SRA attention (fwd, dQ, dK/dV, reduce)", r"sra_"),
-    ("DWConv 3x3 + GELU (fwd_save, bwd_saved)", r"dw2_|dw_"),
+    ("DWConv 3x3 + GELU (fwd_save, bwd_saved, fc1 / fc2-dgrad fused)", r"dw2_mlp_|dw2_|dw_"),
     ("LayerNorm (fwd, bwd)", r"ln_fwd|ln_bwd|rowln"),
     ("AdamW", r"adamw"),
     ("BatchNorm (stats, fold, apply, bwd)", r"bn_"),

@@ -72,7 +72,7 @@ FAMILIES = [
     ("grouped wgrad + reduce (deferred weight gradients)", r"^(gemmk::)?gemm_grouped|^reduce_grouped"),
     ("GEMM (MFMA: linear / conv / decoder / attention projections)", r"^(gemmk::)?(gemm_|splitk_reduce)"),
     ("SRA attention (MFMA)", r"^sra_"),
-    ("depthwise 3x3 conv + GELU (MixFFN)", r"^dw2_|^dw_"),
+    ("depthwise 3x3 conv + GELU (MixFFN; dw2_mlp_*: with fc1 / fc2's dgrad inside)", r"^dw2_mlp_|^dw2_|^dw_"),
     ("Mix-FFN bands (fc1+DW+GELU, fc2 dgrad+DW bwd)", r"^mixffn_"),
     ("LayerNorm", r"^ln_"),
     ("BatchNorm", r"^bn_"),
