@@ -8,7 +8,9 @@ same way into a table of its own, ``OHEM_SIGNATURES``; its entry points are call
 ``EASPP_SIGNATURES``.  ``include/cmx_fcn.h`` (part 4: the fused upsample + loss at the scales of an FCN head)
 likewise, into ``FCN_SIGNATURES``.  ``include/cmx_deeplab.h`` (part 5: the DeepLabV3+ head's wide dilated convolution and
 align-corners upsample + concat) likewise, into ``DEEPLAB_SIGNATURES``.  ``include/cmx_mlp.h`` (part 6: the Mix-FFN of stages
-1-2 with its Linears inside the depthwise kernels) likewise, into ``MLP_SIGNATURES``.
+1-2 with its Linears inside the depthwise kernels) likewise, into ``MLP_SIGNATURES``.  ``include/cmx_uper.h`` (part 7: the
+UPerNet head's pyramid pooling, multi-source upsample + concat, upsample + add and the weight flip of the im2col-free
+input gradient) likewise, into ``UPER_SIGNATURES``.
 
 ``call`` / ``try_call`` / ``query`` / ``refusable`` take an entry point's name and its arguments in
 header order; ``marshal`` converts them by the kind the header declares for each parameter:
@@ -42,6 +44,7 @@ EASPP_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_easpp.h"), os.pa
 FCN_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_fcn.h"), os.path.join(_HERE, "cmx_fcn.h")]
 DEEPLAB_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_deeplab.h"), os.path.join(_HERE, "cmx_deeplab.h")]
 MLP_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_mlp.h"), os.path.join(_HERE, "cmx_mlp.h")]
+UPER_HEADER_PATHS = [os.path.join(_HERE, "..", "include", "cmx_uper.h"), os.path.join(_HERE, "cmx_uper.h")]
 
 
 class CMXError(RuntimeError):
@@ -121,16 +124,18 @@ def _load():
     fcn = parse_header(next(p for p in FCN_HEADER_PATHS if os.path.exists(p)))
     deeplab = parse_header(next(p for p in DEEPLAB_HEADER_PATHS if os.path.exists(p)))
     mlp = parse_header(next(p for p in MLP_HEADER_PATHS if os.path.exists(p)))
-    for table in (sigs, ohem, easpp, fcn, deeplab, mlp):
+    uper = parse_header(next(p for p in UPER_HEADER_PATHS if os.path.exists(p)))
+    for table in (sigs, ohem, easpp, fcn, deeplab, mlp, uper):
         for name, (rt, argt) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argt
             fn.restype = rt
             assert STREAM not in table[name].kinds[:-1], f"{name}: hipStream_t must be the last parameter"
-    return lib, sigs, ohem, easpp, fcn, deeplab, mlp
+    return lib, sigs, ohem, easpp, fcn, deeplab, mlp, uper
 
 
-LIB, SIGNATURES, OHEM_SIGNATURES, EASPP_SIGNATURES, FCN_SIGNATURES, DEEPLAB_SIGNATURES, MLP_SIGNATURES = _load()
+(LIB, SIGNATURES, OHEM_SIGNATURES, EASPP_SIGNATURES, FCN_SIGNATURES, DEEPLAB_SIGNATURES, MLP_SIGNATURES,
+ UPER_SIGNATURES) = _load()
 
 
 def last_error() -> str:
@@ -159,7 +164,7 @@ def _scalar_arg(a):
 _BOUND = {name: (getattr(LIB, name), tuple(_pointer_arg if k == POINTER else _scalar_arg for k in sig.kinds),
                  sig.kinds[-1:] == (STREAM,))
           for name, sig in {**SIGNATURES, **OHEM_SIGNATURES, **EASPP_SIGNATURES, **FCN_SIGNATURES,
-                            **DEEPLAB_SIGNATURES, **MLP_SIGNATURES}.items()}
+                            **DEEPLAB_SIGNATURES, **MLP_SIGNATURES, **UPER_SIGNATURES}.items()}
 
 
 def marshal(name: str, args: tuple) -> tuple:

@@ -28,9 +28,21 @@ def deeplabv3plus_macs(N1, C1, N4, C4, K) -> int:
     return aspp + N1 * (9 * C1 * 48 + 9 * 304 * 256 + 256 * K)
 
 
+def uperhead_macs(grids, K, channels=512, pool_scales=(1, 2, 3, 6)) -> int:
+    """The UPerNet head (decoders/UPernet.py) on the four stage maps ``grids`` = [(N_i pixels, C_i channels)] of one
+    image: the four PPM 1x1 convs on their s x s pooled pixels, the 3x3 bottleneck (C4 + 4 channels) -> channels on
+    the stage-4 grid, three 1x1 laterals, three 3x3 FPN convs, the 3x3 fpn_bottleneck 4 channels -> channels and the
+    classifier on the stage-1 grid."""
+    Ch = channels
+    (N1, _), (N4, C4) = grids[0], grids[3]
+    ppm = sum(s * s for s in pool_scales) * C4 * Ch + N4 * 9 * (C4 + len(pool_scales) * Ch) * Ch
+    fpn = sum(N * (C * Ch + 9 * Ch * Ch) for N, C in grids[:3])
+    return ppm + fpn + N1 * (9 * 4 * Ch * Ch + Ch * K)
+
+
 def forward_macs_per_image(backbone="mit_b2", H=480, W=640, K=40, E=512, decoder="MLPDecoder") -> int:
-    """decoder: "MLPDecoder" (the default; MLPDecoderpp's gate adds no counted op) or "DeepLabV3Plus" (without its
-    auxiliary head)."""
+    """decoder: "MLPDecoder" (the default; MLPDecoderpp's gate adds no counted op), "DeepLabV3Plus" or "UPerHead"
+    (channels = 512, as the builder constructs it), the latter two without their auxiliary head."""
     dims, depths = MIT_SPECS[backbone]["embed_dims"], MIT_SPECS[backbone]["depths"]
     total = 0
     h, w = H, W
@@ -61,6 +73,8 @@ def forward_macs_per_image(backbone="mit_b2", H=480, W=640, K=40, E=512, decoder
     N1 = grids[0][0]
     if decoder == "DeepLabV3Plus":
         return total + deeplabv3plus_macs(N1, grids[0][1], grids[3][0], grids[3][1], K)
+    if decoder == "UPerHead":
+        return total + uperhead_macs(grids, K)
     total += sum(N * C * E for N, C in grids) + N1 * 4 * E * E + N1 * E * K
     return total
 

@@ -800,6 +800,31 @@ class DgradTap:
 IMPLICIT_CONV = os.environ.get("CMX_IMPLICIT_CONV", "1") != "0"
 # CMX_PE1_DIRECT=0 restores the stage-1 im2col + GEMM path (A/B switch for measurements)
 PE1_DIRECT = os.environ.get("CMX_PE1_DIRECT", "1") != "0"
+# CMX_CONV_DGRAD_IMPLICIT=0: a conv that asks for the im2col-free input gradient (ConvF's dgrad_implicit, the
+# UPerNet head's 3x3 convs) takes the dcols + col2im path all the same (A/B switch for measurements)
+CONV_DGRAD_IMPLICIT = os.environ.get("CMX_CONV_DGRAD_IMPLICIT", "1") != "0"
+
+
+def _conv_dgrad_implicit(dy, W, geom):
+    """The input gradient of a stride-1 'same' convolution (odd KH == KW, pad = (K - 1) / 2) without the dcols buffer:
+    dx is itself such a convolution of dy with the flipped, transposed weights (cmx_conv_flip_weight), so it is ONE
+    cmx_conv_implicit_fwd launch that accumulates every tap and channel in fp32 and rounds once (col2im rounds per
+    tap).  16-bit, N % 64 == 0, C % 8 == 0 and the implicit kernel's 31-bit limits; None: not eligible."""
+    G, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, nchw = geom
+    N, NIg = W.shape[1], NI // G
+    M, Kf = NIg * H * Wd, KH * KW * N
+    if not (CONV_DGRAD_IMPLICIT and not nchw and dy.dtype in (torch.bfloat16, torch.float16) and st == 1 and KH == KW
+            and KH % 2 == 1 and 2 * pad == KH - 1 and N % 64 == 0 and C % 8 == 0 and W.shape[-1] == KH * KW * C
+            and M * N < 2 ** 30 and M * C < 2 ** 31 and C * Kf < 2 ** 30):
+        return None
+    Wf = K.conv_flip_weight(W, KH, KW, C)
+    dx = torch.empty(G, M, C, dtype=dy.dtype, device=dy.device)
+    dt = K.dtype_code(dy)
+    sk = K.query("cmx_gemm_splitk", G, M, C, Kf, 0, dt)
+    ws = K._ws(K.query("cmx_gemm_workspace", G, M, C, sk), dy.device) if sk > 1 else None
+    K.call("cmx_conv_implicit_fwd", dy, Wf, dx, None, ws, G, NIg, H, Wd, N, KH, KW, 1, pad, H, Wd, C, M * N,
+           Wf.stride(0), dx.stride(0), 0, sk, dt)
+    return dx
 
 
 class ConvF(Function):
@@ -808,13 +833,15 @@ class ConvF(Function):
     (patch_embed1.hip), else im2col + grouped GEMM."""
 
     @staticmethod
-    def forward(ctx, x, W, Wg, b, bg, geom, anchor, x2=None, dtap=None):
+    def forward(ctx, x, W, Wg, b, bg, geom, anchor, x2=None, dtap=None, dgrad_implicit=False):
         # geom: (G, NI, H, Wd, C, KH, KW, stride, pad, Ho, Wo, nchw); x2: the second image batch
         # of an NCHW input given as two tensors (x holds the first NI - len(x2) images).  dtap: the
-        # DgradTap of the LayerNorm that produced x (its backward takes over the input gradient)
+        # DgradTap of the LayerNorm that produced x (its backward takes over the input gradient).
+        # dgrad_implicit: take the input gradient through _conv_dgrad_implicit where it is eligible
         G, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, nchw = geom
         ctx.x2 = x2
         ctx.dtap = dtap
+        ctx.dgrad_implicit = dgrad_implicit
         ctx.pe1 = None
         Kp = W.shape[-1]
         if IMPLICIT_CONV and not nchw and x.dtype in (torch.bfloat16, torch.float16) and C % 64 == 0 \
@@ -871,7 +898,7 @@ class ConvF(Function):
         if ctx.pe1 is not None:
             # per-workgroup (N, Kp + 1) partial slabs [dW | db], summed by the deferred grouped reduce
             _pe1_wgrad(dy, ctx.pe1, Wg, bg, (G, NI // G, C, H, Wd, KH, KW, st, pad, Ho, Wo), W.shape[1], W.shape[-1])
-            return None, None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None, None
         if ctx.implicit:
             x = cols                 # the conv input (no cols were materialised)
             if not deferred.conv_wgrad(dy, x, Wg, bg, (G, NI // G, H, Wd, C, KH, KW, st, pad, Ho, Wo)):
@@ -891,11 +918,14 @@ class ConvF(Function):
             dx = (torch.empty if exact else torch.zeros)(NI, H, Wd, C, dtype=dy.dtype, device=dy.device)
             dx = K.conv_patch_dgrad(dy, W, dx, (G, NI // G, H, Wd, C, st, Ho, Wo)).view(ctx.xshape)
         elif ctx.needs_input_grad[0] and not nchw:
-            dcols = _dgrad(dy, W, torch.empty(G, NI // G * Ho * Wo, W.shape[-1], dtype=dy.dtype, device=dy.device))
-            dx = torch.empty(NI, H, Wd, C, dtype=dy.dtype, device=dy.device)
-            K.call("cmx_col2im_nhwc", dcols, dx, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, W.shape[-1], K.dtype_code(dx))
+            dx = _conv_dgrad_implicit(dy, W, geom) if ctx.dgrad_implicit else None
+            if dx is None:
+                dcols = _dgrad(dy, W, torch.empty(G, NI // G * Ho * Wo, W.shape[-1], dtype=dy.dtype, device=dy.device))
+                dx = torch.empty(NI, H, Wd, C, dtype=dy.dtype, device=dy.device)
+                K.call("cmx_col2im_nhwc", dcols, dx, NI, H, Wd, C, KH, KW, st, pad, Ho, Wo, W.shape[-1],
+                       K.dtype_code(dx))
             dx = dx.view(ctx.xshape)
-        return dx, None, None, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None, None, None
 
 
 def _pe1_wgrad(dy, imgs, Wg, bg, geom, N, Kp):
@@ -966,7 +996,9 @@ def patch_embed1(store, pe, x, G, NI, H, W, x2=None):
     return layernorm(store, pe.norm, y, G), Ho, Wo
 
 
-def conv(store, mod, x, G, NI, H, W, C, stride, pad, nchw=False, x2=None, dtap=None):
+def conv(store, mod, x, G, NI, H, W, C, stride, pad, nchw=False, x2=None, dtap=None, dgrad_implicit=False):
+    """dgrad_implicit (default off; the UPerNet head turns it on): the input gradient of a stride-1 'same' conv as one
+    im2col-free launch where eligible (_conv_dgrad_implicit), the dcols + col2im path otherwise."""
     KH, KW = mod.kernel_size
     Ho = (H + 2 * pad - KH) // stride + 1
     Wo = (W + 2 * pad - KW) // stride + 1
@@ -977,7 +1009,7 @@ def conv(store, mod, x, G, NI, H, W, C, stride, pad, nchw=False, x2=None, dtap=N
     b = store.w(mod.bias, compute=False).view(G, -1) if mod.bias is not None else None
     bg = store.g(mod.bias).view(G, -1) if mod.bias is not None else None
     geom = (G, NI, H, W, C, KH, KW, stride, pad, Ho, Wo, nchw)
-    return ConvF.apply(x, Wt, Wgt, b, bg, geom, mod.weight, x2, dtap), Ho, Wo
+    return ConvF.apply(x, Wt, Wgt, b, bg, geom, mod.weight, x2, dtap, dgrad_implicit), Ho, Wo
 
 
 # ---------------------------------------------------------------------------- FFM cross attention
@@ -1608,6 +1640,90 @@ class UpcatAcF(Function):
         (B, h, w, H, W), C, Cs = ctx.meta
         dlo, dskip = K.upcat_ac_bwd(_c(dcat), B, h, w, H, W, C, Cs)
         return dlo, dskip, None
+
+
+# ---------------------------------------------------------------------------- UPerNet head (include/cmx_uper.h)
+class ColumnTap:
+    """Side channel from UpcatMultiF's backward to PpmPoolF's: the PPM concat's gradient towards its skip columns (a
+    strided view of dcat, nothing copied), which the pooling backward adds in its own launch (cmx_ppm_pool_bwd's
+    ``add``).  The skip and the pooled branches are the same tensor, so autograd would otherwise add the two terms in
+    a launch of its own."""
+    __slots__ = ("t",)
+
+    def __init__(self):
+        self.t = None
+
+    def put(self, t):
+        self.t = t
+
+    def take(self):
+        t, self.t = self.t, None
+        return t
+
+
+class PpmPoolF(Function):
+    """The pyramid pooling of PPM (UPernet.py:107-146): nn.AdaptiveAvgPool2d(s) of x (B*h*w, C) at up to four scales in
+    one launch each way.  Returns one (B*s*s, C) block per scale, views of one (B * sum s^2, C) buffer in which scale
+    k's block starts at row B * sum_{j<k} s_j^2; the backward puts the blocks' gradients back into one such buffer
+    (one torch.cat of at most B * 256 rows).  tap (ColumnTap, optional): gradient rows of x handed over by the
+    concat's backward, added inside the backward launch."""
+
+    @staticmethod
+    def forward(ctx, x, dims, tap=None):
+        B, h, w, scales = dims
+        ctx.meta = (dims, tap, x.shape[-1], x.dtype)
+        return tuple(K.ppm_pool_fwd(_c(x), B, h, w, scales).split([B * s * s for s in scales]))
+
+    @staticmethod
+    def backward(ctx, *dblocks):
+        (B, h, w, scales), tap, C, dtype = ctx.meta
+        dev = next(d for d in dblocks if d is not None).device
+        dpooled = torch.cat([d if d is not None else torch.zeros(B * s * s, C, dtype=dtype, device=dev)
+                             for d, s in zip(dblocks, scales)])
+        add = tap.take() if tap is not None else None
+        return K.ppm_pool_bwd(dpooled, add, B, h, w, scales), None, None
+
+
+class UpcatMultiF(Function):
+    """torch.cat([skip, up(src_0), ..., up(src_{n-1})], 1), up = bilinear align_corners=False onto (H, W)
+    (UPernet.py:58-66, :94-100), on token rows, one launch each way: skip (B*H*W, Cs), src_i (B*h_i*w_i, C) ->
+    (B*H*W, Cs + n*C).  dims = (B, H, W, ((h_0, w_0), ...)).  tap (ColumnTap, optional): the gradient towards skip is
+    handed over as a view of dcat instead of being copied out, and None is returned for it."""
+
+    @staticmethod
+    def forward(ctx, dims, tap, skip, *srcs):
+        B, H, W, grids = dims
+        skip, srcs = _c(skip), [_c(t) for t in srcs]
+        ctx.meta = (dims, tap, skip.shape[-1], srcs[0].shape[-1])
+        return K.upcat_multi_fwd(skip, srcs, B, H, W, grids)
+
+    @staticmethod
+    def backward(ctx, dcat):
+        (B, H, W, grids), tap, Cs, C = ctx.meta
+        dcat = _c(dcat)
+        dskip, ds = K.upcat_multi_bwd(dcat, B, H, W, Cs, C, grids, want_skip=tap is None)
+        if tap is not None:
+            tap.put(dcat[:, :Cs])
+        return (None, None, dskip, *ds)
+
+
+class UpAddF(Function):
+    """hi + up(lo), the top-down step of the FPN (UPernet.py:78-84) as an out-of-place sum: hi (B*H*W, C), lo (B*h*w, C).
+    Backward: dhi is dout itself; dlo is the gather adjoint cmx_upcat_multi_bwd with no skip columns and one source
+    (exact for any C, where cmx_bilinear_adjoint3 needs C % 128 == 0 in 16 bits)."""
+
+    @staticmethod
+    def forward(ctx, hi, lo, dims):
+        B, h, w, H, W = dims
+        ctx.meta = (dims, hi.shape[-1])
+        return K.up_add_fwd(_c(hi), _c(lo), B, h, w, H, W)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (B, h, w, H, W), C = ctx.meta
+        dout = _c(dout)
+        _, (dlo,) = K.upcat_multi_bwd(dout, B, H, W, 0, C, ((h, w),), want_skip=False)
+        return dout, dlo, None
 
 
 # ---------------------------------------------------------------------------- decoder fuse

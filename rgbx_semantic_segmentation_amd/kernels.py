@@ -529,3 +529,77 @@ def upcat_ac_bwd(dcat, B, h, w, H, W, C, Cs):
     dskip = torch.empty(B * H * W, Cs, dtype=dcat.dtype, device=dcat.device)
     call("cmx_upcat_ac_bwd", dcat, dlo, dskip, B, h, w, H, W, C, Cs, dtype_code(dcat))
     return dlo, dskip
+
+
+# ------------------------------------------------------------------------------ UPerNet head (include/cmx_uper.h)
+def ppm_rows(scales) -> int:
+    """Pooled rows per image of the pyramid pooling at ``scales``: sum of s^2."""
+    return sum(s * s for s in scales)
+
+
+def _scales4(scales):
+    scales = tuple(int(s) for s in scales)
+    return scales + (0,) * (4 - len(scales))
+
+
+def ppm_pool_fwd(x, B, h, w, scales):
+    """pooled (B * sum s^2, C): nn.AdaptiveAvgPool2d(s) of x (B*h*w, C) at up to four scales, one launch; block k
+    starts at row B * sum_{j<k} s_j^2 and holds (B, s_k, s_k, C) (cmx_ppm_pool_fwd)."""
+    C = x.shape[-1]
+    pooled = torch.empty(B * ppm_rows(scales), C, dtype=x.dtype, device=x.device)
+    call("cmx_ppm_pool_fwd", x, pooled, B, h, w, C, *_scales4(scales), dtype_code(x))
+    return pooled
+
+
+def ppm_pool_bwd(dpooled, add, B, h, w, scales):
+    """dx (B*h*w, C) of ppm_pool_fwd on top of ``add`` (B*h*w rows of C at any row stride, or None), one launch
+    (cmx_ppm_pool_bwd)."""
+    C = dpooled.shape[-1]
+    dx = torch.empty(B * h * w, C, dtype=dpooled.dtype, device=dpooled.device)
+    call("cmx_ppm_pool_bwd", dpooled, add, add.stride(0) if add is not None else 0, dx, B, h, w, C, *_scales4(scales),
+         dtype_code(dpooled))
+    return dx
+
+
+def _grids4(grids):
+    flat = [int(v) for g in grids for v in g]
+    return flat + [0] * (8 - len(flat))
+
+
+def upcat_multi_fwd(skip, srcs, B, H, W, grids):
+    """cat (B*H*W, Cs + n*C) = [skip | up(srcs[0]) | ...], bilinear align_corners=False from the sources' own grids
+    ``grids`` = ((h_i, w_i), ...), contiguous operands, one launch (cmx_upcat_multi_fwd); skip None: Cs = 0."""
+    n, C = len(srcs), srcs[0].shape[-1]
+    Cs = skip.shape[-1] if skip is not None else 0
+    cat = torch.empty(B * H * W, Cs + n * C, dtype=srcs[0].dtype, device=srcs[0].device)
+    ps = list(srcs) + [None] * (4 - n)
+    call("cmx_upcat_multi_fwd", skip, *ps, cat, B, H, W, Cs, C, n, *_grids4(grids), dtype_code(cat))
+    return cat
+
+
+def upcat_multi_bwd(dcat, B, H, W, Cs, C, grids, want_skip=True):
+    """(dskip (B*H*W, Cs) or None, [dsrc_i (B*h_i*w_i, C)]) of upcat_multi_fwd, one launch (cmx_upcat_multi_bwd)."""
+    n = len(grids)
+    dskip = torch.empty(B * H * W, Cs, dtype=dcat.dtype, device=dcat.device) if (want_skip and Cs > 0) else None
+    ds = [torch.empty(B * h * w, C, dtype=dcat.dtype, device=dcat.device) for h, w in grids]
+    call("cmx_upcat_multi_bwd", dcat, dskip, *(ds + [None] * (4 - n)), B, H, W, Cs, C, n, *_grids4(grids),
+         dtype_code(dcat))
+    return dskip, ds
+
+
+def up_add_fwd(hi, lo, B, h, w, H, W):
+    """hi (B*H*W, C) + the bilinear align_corners=False upsample of lo (B*h*w, C), in a new tensor (cmx_up_add_fwd)."""
+    out = torch.empty_like(hi)
+    call("cmx_up_add_fwd", hi, lo, out, B, h, w, H, W, hi.shape[-1], dtype_code(hi))
+    return out
+
+
+def conv_flip_weight(W, KH, KW, C):
+    """Wf (G, C, KH*KW*N) with Wf[g][ci][T - 1 - t][co] = W[g][co][t][ci] from the 16-bit tap-major weights W
+    (G, N, KH*KW*C) (cmx_conv_flip_weight, one launch per group): the weights whose stride-1 'same' convolution with
+    dy is the input gradient."""
+    G, N = W.shape[:2]
+    Wf = torch.empty(G, C, KH * KW * N, dtype=W.dtype, device=W.device)
+    for g in range(G):
+        call("cmx_conv_flip_weight", W[g], Wf[g], N, KH, KW, C, W.stride(1), dtype_code(W))
+    return Wf

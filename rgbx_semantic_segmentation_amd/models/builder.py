@@ -42,6 +42,12 @@ Differences by design:
     per GPU (the pooled ASPP branch, as for the eASPP neck); the head's two elementwise Dropouts keep device step counters
     made by the first, eager training forward.  ``forced_masks["dlv3_aspp_dropout"]`` (B, h4, w4, 256) and
     ``forced_masks["dlv3_block_dropout"]`` (B, h1, w1, 256): optional 0/1 masks of those Dropouts for tests.
+  * ``cfg.decoder = "UPerHead"``: the reference's ``UPernet`` branch (builder.py:163-170, decoders.UPernet.UPerHead with
+    channels=512) under its class name; the reference's own spelling stays refused.  Logits at 1/4 resolution, the
+    auxiliary FCNHead beside it BY DEFAULT, as for DeepLabV3Plus.  The forward values are the reference's; its in-place
+    top-down sum makes the reference's own backward raise, so the gradient is that of the out-of-place sum
+    (decoders/UPernet.py).  Training with one image per batch raises ValueError (the scale-1 pooling BatchNorm); the head
+    adds no upper limit on the batch.
   * compute dtype: ``cfg.compute_dtype`` ("float32" | "bfloat16" | "float16"); defaults to
     float16 when ``cfg.use_mixed_precision`` (the reference's fp16 autocast switch,
     config.py:61, train.py:185-198: fp16 storage, fp32 accumulation, with dynamic loss scaling
@@ -62,6 +68,7 @@ from .. import kernels as K
 from ..params import ParamStore
 from .decoders import MLPDecoder, MLPDecoderpp
 from .decoders.MLPDecoder import DecoderHead
+from .decoders.UPernet import UPerHead
 from .decoders.deeplabv3plus import DeepLabV3Plus
 from .decoders.fcnhead import FCNHead
 from .encoders.dual_segformer import BACKBONES, MIT_SPECS, load_dualpath_model
@@ -98,9 +105,10 @@ def backward_segment(name: str) -> int:
 # cfg.decoder (builder.py:154-161 of the reference) -> decode head class
 # "FCNHead": the reference's fallback branch (builder.py:186-189, FCN-32s on the stage-4 map) under an explicit name
 # "DeepLabV3Plus": the reference's 'deeplabv3+' branch (builder.py:172-179) under its class name
+# "UPerHead": the reference's 'UPernet' branch (builder.py:163-170) under its class name
 DECODERS = {"MLPDecoder": MLPDecoder.DecoderHead, "MLPDecoderpp": MLPDecoderpp.DecoderHead, "FCNHead": FCNHead,
-            "DeepLabV3Plus": DeepLabV3Plus}
-AUX_BY_DEFAULT = ("DeepLabV3Plus",)   # builder.py:172-179 builds the auxiliary head beside this decoder
+            "DeepLabV3Plus": DeepLabV3Plus, "UPerHead": UPerHead}
+AUX_BY_DEFAULT = ("DeepLabV3Plus", "UPerHead")   # builder.py:163-179 builds the auxiliary head beside these decoders
 AUX_INDEX, AUX_RATE = 2, 0.4      # builder.py:168-169
 
 SUPPORTED_CRITERIA = ("nn.CrossEntropyLoss(reduction='mean'[, weight=w]), FocalLoss(reduction='mean', gamma == 0 or "
@@ -235,7 +243,9 @@ class EncoderDecoder(nn.Module):
         if decoder not in DECODERS:
             raise NotImplementedError(f"decoder {decoder!r}: only MLPDecoder and MLPDecoderpp are on the CMX hot path" +
                                       (" (the DeepLabV3+ head is selected by its class name, decoder='DeepLabV3Plus')"
-                                       if decoder == "deeplabv3+" else ""))
+                                       if decoder == "deeplabv3+" else
+                                       " (the UPerNet head is selected by its class name, decoder='UPerHead')"
+                                       if decoder == "UPernet" else ""))
         # config.py:57-58 selects the rectify / fusion blocks (dual_segformer.py:316-329: 'FRM' / 'FFM'
         # the originals, any other value the improved IFRM / IFFM, as there)
         frm = _get(cfg, "feature_rectify_module", "FRM")
@@ -260,6 +270,9 @@ class EncoderDecoder(nn.Module):
         elif decoder == "DeepLabV3Plus":   # builder.py:172-179: the reference's constructor, logits on the stage-1 grid
             self.decode_head = DeepLabV3Plus(in_channels=self.channels, num_classes=self.num_classes,
                                              norm_layer=norm_layer)
+        elif decoder == "UPerHead":        # builder.py:163-166: the reference's constructor, logits on the stage-1 grid
+            self.decode_head = UPerHead(in_channels=self.channels, num_classes=self.num_classes,
+                                        norm_layer=norm_layer, channels=512)
         else:
             self.decode_head = DECODERS[decoder](in_channels=self.channels, num_classes=self.num_classes,
                                                  norm_layer=norm_layer,

@@ -37,7 +37,9 @@ CRITERIA = ("CrossEntropyLoss", "FocalLoss", "FocalLoss2d", "CE_Focal", "ProbOhe
 OPTIMIZERS = ("AdamW", "SGDM")
 DECODERS = ("MLPDecoder", "MLPDecoderpp",
             "FCNHead",       # the reference's fallback branch (builder.py:186-189), FCN-32s, under an explicit name
-            "DeepLabV3Plus")  # the reference's 'deeplabv3+' branch (builder.py:172-179) under its class name
+            "DeepLabV3Plus",  # the reference's 'deeplabv3+' branch (builder.py:172-179) under its class name
+            "UPerHead")      # the reference's 'UPernet' branch (builder.py:163-170) under its class name
+AUX_BY_DEFAULT = ("DeepLabV3Plus", "UPerHead")    # the builder's: these decoders come with the auxiliary head
 
 
 def build_parser():
@@ -47,8 +49,8 @@ def build_parser():
     p.add_argument("--aux-head", action="store_true",
                    help="auxiliary FCNHead on the stage-3 map (builder.py:167-170): loss += aux-rate * criterion(aux)")
     p.add_argument("--no-aux-head", action="store_true",
-                   help="--decoder DeepLabV3Plus builds the auxiliary head by default, as the reference does "
-                        "(builder.py:172-179): leave it out")
+                   help="--decoder DeepLabV3Plus / UPerHead build the auxiliary head by default, as the reference does "
+                        "(builder.py:163-179): leave it out")
     p.add_argument("--aux-rate", type=float, default=0.4, help="weight of the auxiliary loss (builder.py:169)")
     p.add_argument("--num-classes", type=int, default=40)
     p.add_argument("--height", type=int, default=480)
@@ -97,14 +99,14 @@ def build_parser():
 
 
 def effective_aux_head(args) -> bool:
-    """--aux-head, or the default of --decoder DeepLabV3Plus unless --no-aux-head."""
-    return bool(getattr(args, "aux_head", False)) or (getattr(args, "decoder", "MLPDecoder") == "DeepLabV3Plus"
+    """--aux-head, or the default of --decoder DeepLabV3Plus / UPerHead unless --no-aux-head."""
+    return bool(getattr(args, "aux_head", False)) or (getattr(args, "decoder", "MLPDecoder") in AUX_BY_DEFAULT
                                                       and not getattr(args, "no_aux_head", False))
 
 
 def build_criterion(args, background=255):
     """The criterion object(s) train.py:70-88 builds for config.criterion; other names raise, and so does a
-    criterion the chosen heads cannot take (--decoder FCNHead / --aux-head, which --decoder DeepLabV3Plus implies
+    criterion the chosen heads cannot take (--decoder FCNHead / --aux-head, which --decoder DeepLabV3Plus / UPerHead imply
     unless --no-aux-head: the builder's message)."""
     criterion = _build_criterion(args, background)
     decoder, aux = getattr(args, "decoder", "MLPDecoder"), effective_aux_head(args)
